@@ -15,8 +15,9 @@ Driver contract: ``python bench.py --gpus N --steps K --warmup W``.  Two ways in
   and prints rank 0's result plus the controller-path launch delays
   (``first_pod_launch_delay_s`` / ``all_pods_launch_delay_s``: job creation ->
   first / last rank Ready, the reference's histograms; measured warm -- ranks
-  forked from the running node's pre-imported zygote -- with ``cold_*`` from a
-  ready-only probe job submitted before the zygote is up; ``comm_init_s`` =
+  forked from the running node's pre-imported zygote; with ``--full`` also
+  ``cold_*`` from a ready-only probe job submitted before the zygote is up,
+  which a plain run leaves out; ``comm_init_s`` =
   the first collective, where the lazy RCCL communicator bootstraps;
   ``pkg/metrics/job_metrics.go:139-194``, observed at
   ``pkg/job_controller/job.go:242-259``).  This process never touches the GPU
@@ -29,6 +30,10 @@ Driver contract: ``python bench.py --gpus N --steps K --warmup W``.  Two ways in
 Either way the timed region is the ranks' own: W untimed warm-up steps, then
 exactly K steps between a barrier + ``synchronize`` on both sides, MAX over
 ranks; ``value`` is whole-job images/s (weak scaling, fixed per-GPU batch).
+``--dump-outputs DIR``: after the timed steps rank 0 writes what the last step
+computed (loss, a seeded sample of the weights and their fp32 masters) to
+``DIR/<name>.npy``; seeds and the synthetic batch are fixed, so two builds run
+with the same arguments compare output for output.
 """
 from __future__ import annotations
 
@@ -54,6 +59,8 @@ def _rank_args(args) -> list:
            "--batch", str(args.batch), "--image", str(args.image), "--bn-backend", args.bn_backend,
            "--conv-benchmark", str(args.conv_benchmark), "--engine", args.engine,
            "--allreduce", args.allreduce]
+    if args.dump_outputs:  # the rank runs in its pod's working directory
+        out += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     if args.cpu:
         out.append("--cpu")
     if args.tiny:
@@ -119,8 +126,9 @@ def launch_job(args) -> int:
     try:
         # 1. cold launch delay: a ready-only job of the same N ranks submitted the
         #    moment the node runtime is up, before the rank zygote can serve it
-        #    (every rank is a fresh interpreter importing torch) -- a node's first job
-        if not args.no_cold_probe:
+        #    (every rank is a fresh interpreter importing torch) -- a node's first job.
+        #    A measurement of its own, so only a --full run makes it
+        if args.full and not args.no_cold_probe:
             probe = mgr.apply(make_job(args, JOB_NAME + "-cold", ready_only=True))
             try:
                 pj = mgr.wait_for_condition("PyTorchJob", "default", JOB_NAME + "-cold", ["Succeeded", "Failed"],
@@ -210,8 +218,11 @@ def main(argv=None) -> int:
     ap.add_argument("--direct", action="store_true",
                     help="run as a single in-process rank (no control plane); WORLD_SIZE forces this too")
     ap.add_argument("--timeout", type=float, default=1800.0, help="job-path wait limit (s)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the job path's cold "
+                         "(pre-zygote) launch delay, from a ready-only probe job of its own")
     ap.add_argument("--no-cold-probe", action="store_true",
-                    help="job path: skip the cold (pre-zygote) ready-only probe job")
+                    help="job path, with --full: skip the cold (pre-zygote) ready-only probe job")
     args = ap.parse_args(argv)
     if "WORLD_SIZE" in os.environ or args.direct:
         if "WORLD_SIZE" not in os.environ:

@@ -51,6 +51,8 @@ def add_args(ap: argparse.ArgumentParser) -> None:
                     help="DP gradient transport for N > 1: RCCL, or the IPC peer-buffer kernel (csrc/p2p.hip)")
     ap.add_argument("--ready-only", action="store_true",
                     help="initialise, signal Ready, exit (bench.py's cold launch-delay probe job)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, rank 0 writes what the last step computed to DIR/<name>.npy")
     ap.add_argument("--cpu", action="store_true", help="CPU/gloo dry run (tests only)")
     ap.add_argument("--tiny", action="store_true", help="tiny ResNet (tests only; invalid metric)")
 
@@ -59,6 +61,36 @@ def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="ResNet-50 DDP bf16 benchmark rank")
     add_args(ap)
     return ap
+
+
+DUMP_SAMPLE = 2_000_000  # elements kept of each flat buffer (8 MB as float32)
+
+
+def dump_outputs(path: str, trainer, loss: float) -> None:
+    """What the last step handed its caller, as ``path/<name>.npy`` in float32:
+    its loss, and the weights it left behind (the bf16 parameters and their
+    fp32 masters) -- of each flat buffer the same seeded sample of
+    ``DUMP_SAMPLE`` positions, so two builds run with the same arguments (same
+    seeds, same synthetic batch) compare element for element.  The BN kernels
+    sum with fp32 atomics, so two runs of one build already differ in the last
+    bits of a step and the difference grows with the steps taken (25 steps,
+    batch 256: loss 2e-4, weights 3e-3 relative); the gradient buffer is
+    scratch of the step, not a result, and is not written."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    sp = trainer.space
+    idx = None
+    if sp.numel > DUMP_SAMPLE:
+        pick = np.sort(np.random.default_rng(0).choice(sp.numel, DUMP_SAMPLE, replace=False))
+        idx = torch.from_numpy(pick).to(sp.param.device)
+    np.save(os.path.join(path, "loss.npy"), np.asarray([loss], dtype=np.float32))
+    for name, t in (("param", sp.param), ("master", sp.master)):
+        t = t.detach().reshape(-1)
+        if idx is not None:
+            t = t[idx]
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
 
 
 def run(args, launcher: str) -> int:
@@ -193,6 +225,8 @@ def run(args, launcher: str) -> int:
         ddp.timing = False
     trainer.check_transport()  # a timed-out P2P all-reduce must fail the run, not report a number
     loss = float(trainer.loss().float().item())
+    if args.dump_outputs and info.rank == 0:
+        dump_outputs(args.dump_outputs, trainer, loss)
 
     step_ms = [evs[i].elapsed_time(evs[i + 1]) for i in range(args.steps)] if evs is not None else []
     n = info.world_size

@@ -31,7 +31,7 @@ def _run(cmd, timeout=600, **env_over):
 
 
 def test_bench_contract_one_rank_cpu():
-    (line,) = _run([sys.executable, "bench.py", "--cpu", "--tiny", "--steps", "2", "--warmup", "1",
+    (line,) = _run([sys.executable, "bench.py", "--full", "--cpu", "--tiny", "--steps", "2", "--warmup", "1",
                     "--batch", "8", "--image", "32"], KDL_ZYGOTE="1")
     assert line["config"]["launcher"] == "kdl-pytorchjob"
     assert line["first_pod_launch_delay_s"] > 0 and line["all_pods_launch_delay_s"] >= line["first_pod_launch_delay_s"]
@@ -99,6 +99,36 @@ def test_bench_direct_path_cpu():
     (line,) = _run([sys.executable, "bench.py", "--direct", "--cpu", "--tiny", "--steps", "2", "--warmup", "1",
                     "--batch", "8", "--image", "32"])
     assert line["n_gpus"] == 1 and line["config"]["launcher"] == "direct"
+
+
+def test_bench_plain_run_dumps_outputs_and_skips_the_cold_probe(tmp_path):
+    """A plain run (no --full) submits no cold probe job; --dump-outputs (a
+    relative DIR, resolved against the caller's directory, not the pod's)
+    leaves the last step's loss and the sampled flat buffers as float32, the
+    same from run to run."""
+    import numpy as np
+    runs = []
+    for d in ("a", "b"):
+        env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="2")
+        env.pop("WORLD_SIZE", None)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--cpu", "--tiny", "--steps", "3",
+                            "--warmup", "1", "--batch", "8", "--image", "32", "--dump-outputs", d],
+                           cwd=tmp_path, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        (line,) = _json_lines(r.stdout)
+        assert KEYS <= set(line) and line["steps"] == 3 and line["ms_per_step"] > 0
+        assert not [k for k in line if k.startswith("cold_")]
+        out = {f[:-4]: np.load(tmp_path / d / f) for f in sorted(os.listdir(tmp_path / d))}
+        assert set(out) == {"loss", "param", "master"}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in out.values())
+        assert out["loss"].shape == (1,) and abs(float(out["loss"][0]) - line["final_loss"]) < 1e-3
+        assert out["param"].shape == out["master"].shape and out["param"].size > 1000
+        assert np.abs(out["master"]).max() > 0
+        # the bf16 weights are the rounded masters
+        assert np.abs(out["param"] - out["master"]).max() <= 2.0 ** -8 * np.abs(out["master"]).max()
+        runs.append(out)
+    for k in runs[0]:
+        np.testing.assert_array_equal(runs[0][k], runs[1][k])
 
 
 def test_bench_job_path_fails_loudly_on_rank_failure():

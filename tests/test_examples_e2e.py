@@ -1,5 +1,5 @@
-"""The reference's own example jobs (``/root/reference/example/*/*.yaml``),
-unchanged, submitted through the control plane (``Manager.apply`` of every
+"""The reference's own example jobs (``example/*/*.yaml`` of its tree, stored
+as fixtures under ``tests/golden/reference_examples``), unchanged, submitted through the control plane (``Manager.apply`` of every
 document, as ``kdl run -f``) and driven to Succeeded by the local runtime.
 
 Each example's image maps to the bundled worker for its framework
@@ -9,8 +9,7 @@ torch.distributed), and the sparse-embedding CTR job with PS + Scheduler +
 Workers (XDL's ``bash -c "exec python mnist.py ... $(TASK_NAME) ..."``
 command exercises the kubelet's $(VAR) expansion and shell-wrapper look-through;
 its ZooKeeper Service/Deployment documents are stored but need no server).
-On this CPU host every rank runs on CPU/gloo; the files are read from the
-reference checkout and the test skips if it is absent.
+The manager is started without GPUs, so every rank runs on CPU/gloo.
 """
 import os
 
@@ -21,7 +20,7 @@ from kubedl_amd.api import common as c
 from kubedl_amd.api import kinds as K
 from kubedl_amd.engine.manager import Manager, ManagerOptions
 
-EXAMPLES = "/root/reference/example"
+EXAMPLES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_examples")
 CASES = [
     ("pytorch/pytorch_job_mnist_mpi.yaml", "PyTorchJob", 3),
     ("tf/tf_job_mnist.yaml", "TFJob", 1),
@@ -33,8 +32,6 @@ CASES = [
 @pytest.mark.parametrize("path,kind,pods", CASES, ids=[c_[1] for c_ in CASES])
 def test_reference_example_runs_to_succeeded(path, kind, pods, tmp_path, monkeypatch):
     f = os.path.join(EXAMPLES, path)
-    if not os.path.exists(f):
-        pytest.skip("reference checkout not present")
     monkeypatch.setenv("KDL_ZYGOTE", "0")
     m = Manager(ManagerOptions(home=str(tmp_path), gpus=0)).start()
     try:
