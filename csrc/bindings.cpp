@@ -527,6 +527,50 @@ at::Tensor gbdt_route(const at::Tensor& bins, const at::Tensor& rows, const at::
   return out;
 }
 
+// margin [N, K] += the leaf values of trees [t0, t1) (tree t -> class t % K), in place (csrc/gbdt_predict.hip).
+// nodes: int32 [n, 4] = GbdtNode (feature, threshold bits, left, value bits); tree_off: int32 [T + 1]
+void gbdt_predict(const at::Tensor& X, const at::Tensor& nodes, const at::Tensor& tree_off, int64_t t0, int64_t t1,
+                  const at::Tensor& margin) {
+  TORCH_CHECK(X.is_cuda() && X.scalar_type() == at::kFloat && X.dim() == 2 && X.is_contiguous() && X.size(1) >= 1,
+              "gbdt_predict: X must be a contiguous fp32 [N, F] GPU tensor");
+  TORCH_CHECK(nodes.is_cuda() && nodes.scalar_type() == at::kInt && nodes.dim() == 2 && nodes.size(1) == 4 &&
+                  nodes.is_contiguous() && nodes.numel() < (int64_t{1} << 31),
+              "gbdt_predict: nodes must be a contiguous int32 [n, 4] GPU tensor");
+  TORCH_CHECK(tree_off.is_cuda() && tree_off.scalar_type() == at::kInt && tree_off.dim() == 1 &&
+                  tree_off.is_contiguous(),
+              "gbdt_predict: tree_off must be a contiguous int32 [T + 1] GPU tensor");
+  TORCH_CHECK(margin.is_cuda() && margin.scalar_type() == at::kFloat && margin.dim() == 2 && margin.is_contiguous() &&
+                  margin.size(0) == X.size(0) && margin.size(1) >= 1 && margin.size(1) <= 32,
+              "gbdt_predict: margin must be a contiguous fp32 [N, K] GPU tensor, 1 <= K <= 32");
+  TORCH_CHECK(nodes.device() == X.device() && tree_off.device() == X.device() && margin.device() == X.device(),
+              "gbdt_predict: tensors on different devices");
+  TORCH_CHECK(0 <= t0 && t0 <= t1 && t1 < tree_off.numel(), "gbdt_predict: tree range [", t0, ", ", t1,
+              ") outside the ", tree_off.numel() - 1, " trees of tree_off");
+  TORCH_CHECK(X.size(1) <= (1 << 20), "gbdt_predict: at most 2^20 features");
+  if (X.size(0) == 0 || t0 == t1) return;
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(X.device());
+  check_hip(kdl::gbdt_predict(X.data_ptr<float>(), X.size(0), static_cast<int>(X.size(1)),
+                              reinterpret_cast<const kdl::GbdtNode*>(nodes.data_ptr<int32_t>()),
+                              static_cast<int>(nodes.size(0)), tree_off.data_ptr<int32_t>(), static_cast<int>(t0),
+                              static_cast<int>(t1), static_cast<int>(margin.size(1)), margin.data_ptr<float>(),
+                              cur_stream()),
+            "gbdt_predict");
+}
+
+// GbdtGrower.heap_packed()'s fp32 [4, heap] -> out int32 [heap, 4] GbdtNodes (left = 2i + 1), no host copy
+void gbdt_heap_nodes(const at::Tensor& packed, const at::Tensor& out) {
+  TORCH_CHECK(packed.is_cuda() && packed.scalar_type() == at::kFloat && packed.dim() == 2 && packed.size(0) == 4 &&
+                  packed.is_contiguous() && packed.size(1) < (1 << 28),
+              "gbdt_heap_nodes: packed must be a contiguous fp32 [4, heap] GPU tensor");
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kInt && out.dim() == 2 && out.size(1) == 4 &&
+                  out.is_contiguous() && out.size(0) == packed.size(1) && out.device() == packed.device(),
+              "gbdt_heap_nodes: out must be a contiguous int32 [heap, 4] tensor on packed's device");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(packed.device());
+  check_hip(kdl::gbdt_heap_to_nodes(packed.data_ptr<float>(), static_cast<int>(packed.size(1)),
+                                    reinterpret_cast<kdl::GbdtNode*>(out.data_ptr<int32_t>()), cur_stream()),
+            "gbdt_heap_to_nodes");
+}
+
 // ------------------------------------------------------------------ CTR
 at::Tensor gemm_bias_act(const at::Tensor& a, const at::Tensor& w, const c10::optional<at::Tensor>& bias, bool relu,
                          bool trans_w) {
@@ -1790,6 +1834,11 @@ PYBIND11_MODULE(_C, m) {
   m.def("set_gbdt_hist_rows", &kdl::set_gbdt_hist_rows, "quantised hist kernel: 0 slot, 4 / 8 row-per-lane (rows in flight), -2 KDL_TUNE");
   m.def("gbdt_split", &gbdt_split, "GBDT best split per (node, feature)");
   m.def("gbdt_route", &gbdt_route, "GBDT row routing (1 = right child)");
+  m.def("gbdt_predict", &gbdt_predict, "forest inference: margin[n, t % K] += tree t's leaf value for t in [t0, t1)");
+  m.def("gbdt_heap_nodes", &gbdt_heap_nodes, "the grower's [4, heap] arrays -> packed forest nodes, on the device");
+  m.def("gbdt_predict_chunk_nodes", &kdl::gbdt_predict_chunk_nodes, "forest nodes per LDS chunk (whole trees)");
+  m.def("gbdt_predict_rows_per_block", &kdl::gbdt_predict_rows_per_block,
+        "rows per block for (F, K): 256 / 128 / 64, 0 = rows not staged in LDS");
   m.def("gemm_bias_act", &gemm_bias_act, "MFMA bf16 GEMM C = act(A W^T + b) (trans_w: A W, W [K, N])",
         py::arg("a"), py::arg("w"), py::arg("bias"), py::arg("relu"), py::arg("trans_w") = false);
   m.def("set_ctr_tile", &kdl::set_ctr_tile, "gemm_bias_act tile: -1 by shape, 0/1/2 = 128x128 / 128x64 / 64x64");

@@ -221,6 +221,25 @@ hipError_t gbdt_route_rows(const uint8_t* bins, const int32_t* rows, const int32
                            const int32_t* split_feat, const int32_t* split_bin, int F, int n,
                            int32_t* go_right, hipStream_t s);
 
+// ---- gbdt_predict.hip (forest inference for HistGBDT.predict and fit's validation margin)
+// a packed node, 16 aligned bytes: feature < 0 = leaf; the right child is left + 1
+struct GbdtNode {
+  int32_t feature;
+  float threshold;
+  int32_t left;
+  float value;
+};
+// margin[n * K + t % K] += leaf value of tree t for t in [t0, t1), in tree order (fp32, no atomics:
+// one lane owns a row's K accumulators).  X [N, F] fp32 row-major; nodes: every tree's nodes, tree t at
+// [tree_off[t], tree_off[t + 1]) with child indices relative to the tree; 1 <= K <= 32
+// (a tree whose offsets leave [0, num_nodes] adds nothing)
+hipError_t gbdt_predict(const float* X, int64_t N, int F, const GbdtNode* nodes, int num_nodes,
+                        const int32_t* tree_off, int t0, int t1, int K, float* margin, hipStream_t s);
+int gbdt_predict_chunk_nodes();                  // nodes per LDS chunk (whole trees; a larger tree is read from global)
+int gbdt_predict_rows_per_block(int F, int K);   // 256 / 128 / 64, or 0: rows not staged in LDS
+// the grower's [4, heap] fp32 (feature, split bin, threshold, value) -> heap GbdtNodes (left = 2i + 1)
+hipError_t gbdt_heap_to_nodes(const float* packed, int heap, GbdtNode* out, hipStream_t s);
+
 // ---- ctr.hip (XDLJob CTR model: MFMA GEMM, embeddings, sparse Adagrad)
 // b_kn: B is [K][N] (C = A B), else [N][K] (C = A B^T)
 hipError_t gemm_bias_act(const void* A, const void* B, const void* bias, bool bias_bf16, void* C, int M, int N, int K,

@@ -28,9 +28,18 @@ Every rank holds a row shard; all ranks grow identical trees because they
 see identical all-reduced histograms.  On CPU (or without the extension)
 the same algorithm runs on torch ops -- that path is the numerics reference
 for the kernels in tests.
+
+Inference: ``predict`` packs the trees into a node table once and runs the
+forest kernel (csrc/gbdt_predict.hip: one lane per row, rows and whole trees
+staged in LDS, leaves added in tree order -- bit-identical to
+``predict_margin``, the torch traversal, which is also the CPU path).  The
+same kernel over a tree range advances the validation margin of
+``fit(eval_set=...)`` straight from the grower's heap arrays (early stopping,
+``evals_result``).  ``save`` / ``load`` keep a model as JSON.
 """
 from __future__ import annotations
 
+import json
 import math
 import os
 import time
@@ -55,6 +64,7 @@ class GBDTParams:
     gamma: float = 0.0
     min_child_weight: float = 1.0
     base_score: float = 0.5
+    early_stopping_rounds: int = 0  # 0 = off (fit's ``early_stopping_rounds`` argument overrides it)
 
     @classmethod
     def parse(cls, spec: str, **kw) -> "GBDTParams":
@@ -116,6 +126,12 @@ class HistGBDT:
             _ext.require_on_gpu("HistGBDT")
             self.use_hip = False
         self.stats = {"hist_builds": 0, "hist_subtracted": 0}
+        # fit(eval_set=...): the validation metric per round; with early stopping the best round
+        self.evals_result: List[float] = []
+        self.eval_metric: Optional[str] = None
+        self.best_iteration: Optional[int] = None
+        self.best_score: Optional[float] = None
+        self._forest_cache = None  # (key, trees kept alive, nodes, tree_off, max feature): _forest()
 
     # ------------------------------------------------------------ quantisation
     def fit_cuts(self, X: torch.Tensor, sample: int = 65536, seed: int = 0) -> None:
@@ -395,10 +411,20 @@ class HistGBDT:
             torch.cuda.synchronize(self.device)
         return time.perf_counter()
 
-    def fit(self, X: torch.Tensor, y: torch.Tensor, log_every: int = 0, callback=None):
+    def fit(self, X: torch.Tensor, y: torch.Tensor, log_every: int = 0, callback=None, eval_set=None,
+            early_stopping_rounds: Optional[int] = None):
         """``stats['setup_s']``: host->device copy, cut fitting, quantisation and the
         grower's workspaces; ``stats['boost_s']``: the boosting rounds alone (one
-        synchronisation at each end, none inside)."""
+        synchronisation at each end, none inside).
+
+        ``eval_set=(Xv, yv)``: a held-out set (this rank's shard of it) whose margin is
+        advanced by each round's trees; ``evals_result[i]`` is the objective's metric
+        (``eval_metric``: rmse / logloss / mlogloss) after round ``i``, from loss sums
+        all-reduced over the ranks.  Without ``early_stopping_rounds`` the sums stay
+        on the device until the end of ``fit`` (one copy); with it one value is read
+        per round, training stops once the metric has not improved for that many
+        rounds (every rank at the same round), ``best_iteration`` / ``best_score``
+        are set, all grown trees are kept and ``predict`` defaults to the best round."""
         t0 = self._sync_time()
         host_cuts = {}
         th = None
@@ -439,6 +465,7 @@ class HistGBDT:
                      ("setup_grower_s", t1 - tc)):
             self.stats[k] = self.stats.get(k, 0.0) + v
         dev_trees = []
+        ev = self._eval_begin(eval_set, early_stopping_rounds, grower) if eval_set is not None else None
         for it in range(self.p.n_estimators):
             g_all, h_all = self._grad_hess(pred, y)
             round_trees = []
@@ -459,6 +486,10 @@ class HistGBDT:
                 self.trees.append(round_trees)
             if callback is not None:
                 callback(it, pred)
+            if ev is not None and self._eval_round(ev, it, round_trees):
+                break
+        if ev is not None:
+            self._eval_end(ev)
         t2 = self._sync_time()
         self.stats["setup_s"] = self.stats.get("setup_s", 0.0) + (t1 - t0)
         self.stats["boost_s"] = self.stats.get("boost_s", 0.0) + (t2 - t1)
@@ -477,10 +508,90 @@ class HistGBDT:
                 raise RuntimeError(f"GBDT route+scan: {faults} look-back timeouts (csrc/gbdt.hip route_scan_kernel)")
         return pred
 
-    def predict_margin(self, X: torch.Tensor) -> torch.Tensor:
-        X = X.to(self.device).float()
-        pred = self._base(X.shape[0])
-        for round_trees in self.trees:
+    # ------------------------------------------------------------ validation set (fit(eval_set=...))
+    def _num_class(self) -> int:
+        return self.p.num_class if self.p.objective.startswith("multi:") else 1
+
+    def _loss_sum(self, margin: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        """The sum over rows of ``metric``'s per-row loss (squared error for rmse), one
+        fp64 scalar on the device."""
+        obj = self.p.objective
+        if obj.startswith("multi:"):
+            pr = torch.softmax(margin, 1)
+            row = -torch.log(pr.gather(1, y.long()[:, None]).clamp_min(1e-15))
+        elif obj == "binary:logistic":
+            pr = torch.sigmoid(margin[:, 0])
+            yy = y.float()
+            row = -(yy * torch.log(pr.clamp_min(1e-15)) + (1 - yy) * torch.log((1 - pr).clamp_min(1e-15)))
+        else:
+            row = (margin[:, 0] - y.float()) ** 2
+        return row.sum(dtype=torch.float64)
+
+    def _eval_begin(self, eval_set, early_stopping_rounds, grower) -> dict:
+        Xv, yv = eval_set
+        Xv = Xv.to(self.device).float().contiguous()
+        yv = yv.to(self.device)
+        if Xv.dim() != 2 or Xv.shape[1] != self.cuts.shape[0] or yv.shape[0] != Xv.shape[0]:
+            raise ValueError(f"eval_set: Xv {tuple(Xv.shape)} / yv {tuple(yv.shape)} do not match the "
+                             f"{self.cuts.shape[0]} training features")
+        K = self._num_class()
+        esr = self.p.early_stopping_rounds if early_stopping_rounds is None else early_stopping_rounds
+        obj = self.p.objective
+        self.eval_metric = "mlogloss" if obj.startswith("multi:") else "logloss" if obj == "binary:logistic" else "rmse"
+        self.evals_result = []
+        self.best_iteration = self.best_score = None
+        ev = {"X": Xv, "y": yv, "margin": self._base(Xv.shape[0]), "sums": [], "esr": int(esr or 0),
+              "best": math.inf, "best_it": 0,
+              # the validation rows of every rank, reduced once
+              "count": _allreduce_(torch.tensor([float(Xv.shape[0])], dtype=torch.float64, device=self.device))}
+        if ev["esr"] > 0:
+            ev["count_host"] = float(ev["count"])  # read once, before the rounds
+        if grower is not None:
+            heap = (1 << (self.p.max_depth + 1)) - 1
+            ev["heap"] = heap
+            ev["nodes"] = torch.empty(K * heap, 4, dtype=torch.int32, device=self.device)
+            ev["off"] = torch.arange(K + 1, dtype=torch.int32, device=self.device) * heap
+        return ev
+
+    def _eval_value(self, loss_sum: float, count: float) -> float:
+        m = loss_sum / max(count, 1.0)
+        return math.sqrt(m) if self.eval_metric == "rmse" else m
+
+    def _eval_round(self, ev: dict, it: int, round_trees) -> bool:
+        """Add this round's trees to the validation margin and record its loss sum;
+        True = stop training (early stopping)."""
+        if "nodes" in ev:
+            # the device grower's heap arrays -> packed nodes -> range kernel: no host copy
+            ext, heap = _ext.load(), ev["heap"]
+            for k, packed in enumerate(round_trees):
+                ext.gbdt_heap_nodes(packed, ev["nodes"][k * heap:(k + 1) * heap])
+            if ev["X"].shape[0]:
+                ext.gbdt_predict(ev["X"], ev["nodes"], ev["off"], 0, len(round_trees), ev["margin"])
+        else:
+            self._add_trees_torch(ev["X"], ev["margin"], [round_trees])
+        s = _allreduce_(self._loss_sum(ev["margin"], ev["y"]).view(1))
+        ev["sums"].append(s)
+        if ev["esr"] <= 0:
+            return False
+        v = self._eval_value(float(s), ev["count_host"])  # the one small read of the round
+        if v < ev["best"]:
+            ev["best"], ev["best_it"] = v, it
+            return False
+        return it - ev["best_it"] >= ev["esr"]
+
+    def _eval_end(self, ev: dict) -> None:
+        if not ev["sums"]:
+            return
+        host = torch.cat(ev["sums"] + [ev["count"]]).tolist()  # one copy for every round
+        self.evals_result = [self._eval_value(v, host[-1]) for v in host[:-1]]
+        if ev["esr"] > 0:
+            self.best_iteration, self.best_score = ev["best_it"], ev["best"]
+
+    # ------------------------------------------------------------ prediction
+    def _add_trees_torch(self, X: torch.Tensor, pred: torch.Tensor, rounds) -> torch.Tensor:
+        """pred[:, k] += each round's tree k, in order: the torch traversal (the CPU
+        path and the numerics reference of csrc/gbdt_predict.hip)."""
+        for round_trees in rounds:
             for k, t in enumerate(round_trees):
                 feat = torch.tensor(t.feature, device=self.device)
                 thr = torch.tensor(t.threshold, device=self.device, dtype=torch.float32)
@@ -498,6 +609,171 @@ class HistGBDT:
                     node = torch.where(leafm, node, nxt)
                 pred[:, k] += val[node]
         return pred
+
+    def predict_margin(self, X: torch.Tensor) -> torch.Tensor:
+        X = X.to(self.device).float()
+        return self._add_trees_torch(X, self._base(X.shape[0]), self.trees)
+
+    @staticmethod
+    def _pack_tree(t: Tree):
+        """One tree as (feature, threshold, left, value) numpy arrays in node-table
+        form: the children of a split are the adjacent pair (left, left + 1), both
+        after their parent.  Both growers number nodes that way; a tree that does
+        not (a loaded file) is renumbered as a whole, breadth first."""
+        import numpy as np
+        n = len(t.value)
+        feat = np.asarray(t.feature, dtype=np.int64)
+        left = np.asarray(t.left, dtype=np.int64)
+        right = np.asarray(t.right, dtype=np.int64)
+        thr = np.asarray(t.threshold, dtype=np.float32)
+        val = np.asarray(t.value, dtype=np.float32)
+        if n == 0 or not (len(feat) == len(left) == len(right) == len(thr) == n):
+            raise ValueError(f"tree with inconsistent node arrays (value {n}, feature {len(feat)}, left {len(left)}, "
+                             f"right {len(right)}, threshold {len(thr)})")
+        split = feat >= 0
+        idx = np.arange(n)
+        if ((left[split] < 0) | (left[split] >= n) | (right[split] < 0) | (right[split] >= n)).any():
+            raise ValueError("tree with a child index outside its node list")
+        if not ((right[split] == left[split] + 1) & (left[split] > idx[split])).all():
+            order, seen, q = [0], {0}, 0
+            while q < len(order):  # breadth first: children get the next two ids
+                i = order[q]
+                q += 1
+                if feat[i] >= 0:
+                    for c in (int(left[i]), int(right[i])):
+                        if c in seen:
+                            raise ValueError("tree whose nodes are shared or form a cycle")
+                        seen.add(c)
+                        order.append(c)
+            order = np.asarray(order)
+            new = np.full(n, -1, dtype=np.int64)
+            new[order] = np.arange(len(order))
+            feat, thr, val = feat[order], thr[order], val[order]
+            left = new[left[order]]
+            split = feat >= 0
+        left = np.where(split, left, -1)
+        return feat.astype(np.int32), thr, left.astype(np.int32), val
+
+    def _forest(self):
+        """The packed forest on the device: nodes int32 [n, 4] (GbdtNode of
+        csrc/kdl_api.h), tree_off int32 [T + 1], tree ``t`` = round ``t // K``, class
+        ``t % K``.  Cached; rebuilt when ``trees`` holds other Tree objects (a Tree
+        edited in place is not noticed: assign a new one)."""
+        import numpy as np
+        K = self._num_class()
+        flat = []
+        for r in self.trees:
+            if len(r) != K:
+                raise ValueError(f"a boosting round with {len(r)} trees in a {K}-class model")
+            flat += r
+        key = (str(self.device), tuple(id(t) for t in flat))
+        c = self._forest_cache
+        if c is not None and c[0] == key:
+            return c[2], c[3], c[4]
+        parts = [self._pack_tree(t) for t in flat]
+        off = np.zeros(len(parts) + 1, dtype=np.int64)
+        if parts:
+            off[1:] = np.cumsum([len(p[0]) for p in parts])
+        if off[-1] >= 2 ** 31:
+            raise ValueError("forest of 2^31 or more nodes")
+        nodes = np.empty((int(off[-1]), 4), dtype=np.int32)
+        if parts:
+            nodes[:, 0] = np.concatenate([p[0] for p in parts])
+            nodes[:, 1] = np.concatenate([p[1] for p in parts]).view(np.int32)
+            nodes[:, 2] = np.concatenate([p[2] for p in parts])
+            nodes[:, 3] = np.concatenate([p[3] for p in parts]).view(np.int32)
+        max_feat = int(nodes[:, 0].max()) if len(nodes) else -1
+        d_nodes = torch.from_numpy(nodes).to(self.device)
+        d_off = torch.from_numpy(off.astype(np.int32)).to(self.device)
+        self._forest_cache = (key, flat, d_nodes, d_off, max_feat)
+        return d_nodes, d_off, max_feat
+
+    def predict(self, X: torch.Tensor, output_margin: bool = False, n_rounds: Optional[int] = None) -> torch.Tensor:
+        """Batch prediction with the first ``n_rounds`` rounds (default: up to the best
+        round of an early-stopped fit, else all).  ``output_margin=True`` returns the
+        raw margin [N, K] (``predict_margin``'s result, bit for bit); otherwise the
+        objective's transform: probabilities [N] (``binary:logistic``, sigmoid),
+        [N, K] (``multi:softprob``, softmax) or the value [N] (regression).  On the
+        GPU this is the forest kernel of csrc/gbdt_predict.hip, on CPU the torch
+        traversal."""
+        if X.dim() != 2:
+            raise ValueError(f"predict: X must be [N, F], got {tuple(X.shape)}")
+        if self.cuts is not None and X.shape[1] != self.cuts.shape[0]:
+            raise ValueError(f"predict: X has {X.shape[1]} features, the model was fitted on {self.cuts.shape[0]}")
+        total = len(self.trees)
+        if n_rounds is None:
+            n_rounds = total if self.best_iteration is None else self.best_iteration + 1
+        if not 0 <= n_rounds <= total:
+            raise ValueError(f"predict: n_rounds {n_rounds} outside the model's {total} rounds")
+        X = X.to(self.device).float().contiguous()
+        margin = self._base(X.shape[0])
+        if self.use_hip and X.is_cuda:
+            nodes, off, max_feat = self._forest()
+            if max_feat >= X.shape[1]:
+                raise ValueError(f"predict: the trees split on feature {max_feat}, X has {X.shape[1]} features")
+            _ext.load().gbdt_predict(X, nodes, off, 0, n_rounds * margin.shape[1], margin)
+        else:
+            self._add_trees_torch(X, margin, self.trees[:n_rounds])
+        return margin if output_margin else self.transform_margin(margin)
+
+    def transform_margin(self, margin: torch.Tensor) -> torch.Tensor:
+        """The objective's output transform of a raw margin [N, K] (see ``predict``)."""
+        if self.p.objective.startswith("multi:"):
+            return torch.softmax(margin, 1)
+        if self.p.objective == "binary:logistic":
+            return torch.sigmoid(margin[:, 0])
+        return margin[:, 0]
+
+    # ------------------------------------------------------------ model file
+    FORMAT_VERSION = 1
+
+    def save(self, path: str) -> None:
+        """The model as JSON: ``params``, ``cuts`` ([F, B-1]) and ``trees`` (per round,
+        per class, the Tree arrays), plus ``version``.  Infinite thresholds are
+        written as JSON's ``Infinity`` extension, which ``load`` reads back."""
+        doc = {"version": self.FORMAT_VERSION, "params": dict(self.p.__dict__),
+               "cuts": None if self.cuts is None else self.cuts.cpu().tolist(),
+               "trees": [[dict(t.__dict__) for t in r] for r in self.trees]}
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as f:
+            json.dump(doc, f)
+
+    @classmethod
+    def load(cls, path: str, device=None) -> "HistGBDT":
+        with open(path) as f:
+            doc = json.load(f)
+        missing = [k for k in ("params", "cuts", "trees") if k not in doc]
+        if missing:
+            raise ValueError(f"{path}: not a HistGBDT model file (no {', '.join(missing)})")
+        if int(doc.get("version", 1)) > cls.FORMAT_VERSION:
+            raise ValueError(f"{path}: model file version {doc['version']} is newer than this code reads "
+                             f"({cls.FORMAT_VERSION})")
+        known = GBDTParams.__dataclass_fields__
+        m = cls(GBDTParams(**{k: v for k, v in doc["params"].items() if k in known}), device)
+        if doc["cuts"] is not None:
+            m.cuts = torch.tensor(doc["cuts"], dtype=torch.float32, device=m.device)
+            if m.cuts.dim() != 2:
+                raise ValueError(f"{path}: cuts must be [features, bins - 1]")
+        K = m._num_class()
+        fields = Tree.__dataclass_fields__
+        for ri, r in enumerate(doc["trees"]):
+            if len(r) != K:
+                raise ValueError(f"{path}: round {ri} has {len(r)} trees, the objective needs {K}")
+            trees = []
+            for k, d in enumerate(r):
+                if set(d) != set(fields):
+                    raise ValueError(f"{path}: round {ri} tree {k}: expected the arrays {sorted(fields)}")
+                t = Tree(**{name: list(d[name]) for name in fields})
+                try:
+                    feat = cls._pack_tree(t)[0]
+                except ValueError as e:
+                    raise ValueError(f"{path}: round {ri} tree {k}: {e}") from None
+                if m.cuts is not None and len(feat) and int(feat.max()) >= m.cuts.shape[0]:
+                    raise ValueError(f"{path}: round {ri} tree {k} splits on feature {int(feat.max())}, but the "
+                                     f"model has only {m.cuts.shape[0]} features (rows of cuts)")
+                trees.append(t)
+            m.trees.append(trees)
+        return m
 
     def metric(self, pred: torch.Tensor, y: torch.Tensor) -> dict:
         obj = self.p.objective
