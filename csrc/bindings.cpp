@@ -1205,6 +1205,14 @@ void apply_fin_arm(const FinArm& f, kdl::Conv1x1Args& a, int64_t N, int64_t epi)
   if (!f.ws) return;
   TORCH_CHECK(f.C == N, "bn_fin_arm: armed for C = ", f.C, ", the GEMM has N = ", N);
   TORCH_CHECK(epi == 1 || epi == 2 || epi == 3, "bn_fin_arm: the GEMM's epilogue produces no BN sums");
+  // the finalize sums the armed workspace's own replicas: sums added anywhere else would be
+  // left behind and the coefficients computed from zeros
+  const float* want = f.ws + (epi == 1 ? 0 : 32 * 2 * f.C);
+  TORCH_CHECK(a.acc == want, "bn_fin_arm: the GEMM's acc is not the armed workspace's ",
+              epi == 1 ? "forward" : "backward", " replica block");
+  if (f.ws2)
+    TORCH_CHECK(epi == 3 && a.acc2 == f.ws2 + 32 * 2 * f.C,
+                "bn_fin_arm: the GEMM's acc2 is not the second armed workspace's backward replica block");
   a.fin_ws = f.ws;
   a.fin_ws2 = f.ws2;
   a.fin_M = f.M;

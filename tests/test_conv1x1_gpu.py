@@ -184,7 +184,7 @@ def _bwd_ws(C, dev, seed):
     return ws
 
 
-@pytest.mark.parametrize("epi", [0, 2, 3])
+@pytest.mark.parametrize("epi", [0, 2, 3, 4])
 @pytest.mark.parametrize("M,N,K", [(3000, 64, 256), (700, 512, 2048), (1100, 256, 64), (513, 128, 512)])
 def test_gemm_bwd_apply_prologue_bit_exact(epi, M, N, K):
     """csrc/conv1x1.hip PRO_BWD: the armed dgrad GEMM on (g, x) equals the
@@ -207,23 +207,25 @@ def test_gemm_bwd_apply_prologue_bit_exact(epi, M, N, K):
         kw = dict(ex=torch.randn(M, N, device=dev).bfloat16(), emean=torch.randn(N, device=dev),
                   eres=torch.randn(M, N, device=dev).bfloat16(),
                   ebits=torch.randint(0, 256, (M, N // 8), device=dev, dtype=torch.uint8))
+    elif epi == 4:
+        kw = dict(eres=torch.randn(M, N, device=dev).bfloat16())
     old = ext.get_gemm_core()
     ext.set_gemm_core(0)
     try:
         ref = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
         ws_r = _ws(N, dev)
-        _gemm(dc, wt, ref, M, N, K, epi=epi, acc=ws_r if epi else None, **kw)
+        _gemm(dc, wt, ref, M, N, K, epi=epi, acc=ws_r if epi in (2, 3) else None, **kw)
         out = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
         thru = torch.full((M, K), float("nan"), device=dev, dtype=torch.bfloat16)
         ws_f = _ws(N, dev)
         ext.bn_bwd_pro_arm(x, wsb, K, thru)
-        _gemm(g, wt, out, M, N, K, epi=epi, acc=ws_f if epi else None, **kw)
+        _gemm(g, wt, out, M, N, K, epi=epi, acc=ws_f if epi in (2, 3) else None, **kw)
     finally:
         ext.set_gemm_core(old)
     torch.cuda.synchronize()
     assert torch.equal(thru.view(torch.int16), dc.view(torch.int16))
     assert torch.equal(out.view(torch.int16), ref.view(torch.int16))
-    if epi:
+    if epi in (2, 3):
         a, b = (w[:REP * 2 * N].view(REP, 2, N).sum(0) for w in (ws_f, ws_r))
         torch.testing.assert_close(a, b, atol=1e-2, rtol=1e-4)
     # and against an fp32 reference of the whole op (apply, then the plain GEMM)
