@@ -939,6 +939,41 @@ void a2a_owner_update(const at::Tensor& grads, const at::Tensor& local, int64_t 
 
 int64_t dedup_table_slots(int64_t n) { return kdl::dedup_table_slots(static_cast<int>(n)); }
 
+// CTR evaluation (csrc/ctr_eval.hip): add n rows into the streaming-AUC state
+static void check_auc_hist(const at::Tensor& hist, const char* who) {
+  TORCH_CHECK(hist.is_cuda() && hist.scalar_type() == at::kLong && hist.is_contiguous() && hist.dim() == 2 &&
+                  hist.size(0) == 2 && hist.size(1) == 65536 &&
+                  reinterpret_cast<uintptr_t>(hist.data_ptr()) % 16 == 0,
+              who, ": hist int64 [2, 65536] contiguous");
+}
+
+void auc_accumulate(const at::Tensor& logit, const at::Tensor& y, at::Tensor hist, at::Tensor invalid) {
+  TORCH_CHECK(logit.is_cuda() && logit.scalar_type() == at::kFloat && logit.dim() == 1 && logit.is_contiguous(),
+              "auc_accumulate: logit f32 [n] contiguous");
+  TORCH_CHECK(y.is_cuda() && y.scalar_type() == at::kFloat && y.dim() == 1 && y.is_contiguous() &&
+                  y.numel() == logit.numel(),
+              "auc_accumulate: labels f32 [n] contiguous");
+  check_auc_hist(hist, "auc_accumulate");
+  TORCH_CHECK(invalid.is_cuda() && invalid.scalar_type() == at::kLong && invalid.numel() == 1 &&
+                  invalid.is_contiguous(),
+              "auc_accumulate: invalid int64 [1]");
+  TORCH_CHECK(y.get_device() == logit.get_device() && hist.get_device() == logit.get_device() &&
+                  invalid.get_device() == logit.get_device(),
+              "auc_accumulate: one device");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(logit.device());
+  check_hip(kdl::auc_accumulate(logit.data_ptr<float>(), y.data_ptr<float>(), logit.numel(),
+                                hist.data_ptr<int64_t>(), invalid.data_ptr<int64_t>(), cur_stream()),
+            "auc_accumulate");
+}
+
+at::Tensor auc_finalize(const at::Tensor& hist) {
+  check_auc_hist(hist, "auc_finalize");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(hist.device());
+  auto out = at::empty({3}, hist.options());
+  check_hip(kdl::auc_finalize(hist.data_ptr<int64_t>(), out.data_ptr<int64_t>(), cur_stream()), "auc_finalize");
+  return out;
+}
+
 // the CSR half of dedup_csr, later in the step (sizes from that dedup_csr call;
 // sizes and cursor are scratch of the long-segment sort afterwards)
 void csr_from_inverse_only(const at::Tensor& inv, at::Tensor sizes, const at::Tensor& count, at::Tensor bsum,
@@ -1882,6 +1917,10 @@ PYBIND11_MODULE(_C, m) {
         py::arg("dense") = py::none(), py::arg("tail") = 0);
   m.def("segment_adagrad", &segment_adagrad, "segment sum + fused sparse Adagrad on owned rows");
   m.def("dedup_table_slots", &dedup_table_slots, "hash-table slots dedup_csr needs for n ids");
+  m.def("auc_accumulate", &auc_accumulate,
+        "streaming AUC: add rows (logit f32 [n], y f32 [n]) into hist int64 [2, 65536] / invalid int64 [1]");
+  m.def("auc_finalize", &auc_finalize, "streaming AUC: (U2, P, N) int64 [3] of a histogram");
+  m.def("auc_rows_per_block", &kdl::auc_rows_per_block, "rows one auc_accumulate block counts in LDS for n rows");
   m.def("segment_reduce_adagrad", &segment_reduce_adagrad,
         "one-owner sync-free push: per-id gradient sums (segment_reduce) applied by Adagrad in the same launch");
   m.def("csr_from_inverse_only", &csr_from_inverse_only, "CSR (seg, order) of a dedup_csr inverse, positions ascending per id");

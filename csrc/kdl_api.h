@@ -332,6 +332,18 @@ int csr_bsum_slots(int n);
 hipError_t csr_from_inverse(const int64_t* inv, int n, int* sizes, const int* count, int* bsum, int* cursor,
                             int64_t* seg, int64_t* order, hipStream_t s);
 
+// CTR evaluation (csrc/ctr_eval.hip): streaming AUC over a 65,536-bucket integer
+// histogram keyed on the top 16 bits of the ordered bit pattern of the fp32 logit.
+// hist int64 [2, 65536] (row 0 negatives, row 1 positives: y > 0.5), invalid
+// int64 [1] (NaN logits, excluded from hist); both are added to.  n = 0 launches
+// nothing.  Kernels only: no memset / memcpy.
+int64_t auc_rows_per_block(int64_t n);  // rows one block counts in LDS (< 65536)
+hipError_t auc_accumulate(const float* logit, const float* y, int64_t n, int64_t* hist, int64_t* invalid,
+                          hipStream_t s);
+// out int64 [3] = (U2, P, N), U2 = sum_b neg[b] * (2 * sum_{c > b} pos[c] + pos[b]);
+// exact for P, N < 2^31 (U2 < 2^63).  hist 16-byte aligned.
+hipError_t auc_finalize(const int64_t* hist, int64_t* out, hipStream_t s);
+
 
 // ---- conv1x1.hip (ResNet 1x1 convs as MFMA GEMMs with fused BN prologue/epilogues)
 // epi: 0 plain, 1 BN-forward stats, 2 ReLU-mask-from-x + BN-backward sums,

@@ -26,6 +26,12 @@ MI355X-first re-design:
   loss (``head_bce_fwd/bwd``: a GEMV per row + loss + dlogit in one pass,
   dx / dw / db in one backward pass) -- no vendor GEMM in the step.
 
+* **Evaluation without side effects.**  ``CTRModel.evaluate`` scores a
+  held-out batch forward only (``DenseTower.logits``: the training forward's
+  launches, nothing kept), feeds a streaming AUC (``kubedl_amd.ops.auc``,
+  csrc/ctr_eval.hip) and ends the pull without a push
+  (``ShardedEmbedding.discard_pull``; PS ranks: ``participate_pull``).
+
 On CPU (tests) every op has a torch composition with the same semantics.
 """
 from __future__ import annotations
@@ -299,6 +305,25 @@ class DenseTower(nn.Module):
         for l in self.layers:
             x = l(x)
         return head_bce(x, self.head.weight, self.head.bias, y)
+
+    @torch.no_grad()
+    def logits(self, x, y=None):
+        """Forward only (evaluation): (logits fp32 [B], mean BCE loss or None without
+        labels).  The fused path issues the launches of ``train_step``'s forward
+        (``gemm_bias_act`` per layer, then ``head_bce_fwd``; zero labels stand in
+        when ``y`` is None) and keeps no activation; otherwise the torch forward
+        of ``loss``.  Either way the logits are bit-identical to ``loss``'s."""
+        has_y = y is not None
+        if not has_y:
+            y = torch.zeros(x.shape[0], device=x.device)
+        if self.fused_ok(x):
+            a = x.contiguous()
+            for l in self.layers:
+                a = _ext.load().gemm_bias_act(a, l.weight.contiguous(), l.bias, bool(l.relu))
+            loss, logit, _dlogit = _head_fwd(a, self.head.weight, self.head.bias, y)
+            return logit, (loss.view(()) if has_y else None)
+        loss, logit = self.loss(x.detach(), y)
+        return logit, (loss if has_y else None)
 
 
 # ---------------------------------------------------------------- sparse embedding
@@ -776,6 +801,8 @@ class ShardedEmbedding:
     def push(self, grad_unique: torch.Tensor, scale: float = 1.0) -> None:
         """grad rows aligned with the unique ids of the last pull."""
         ctx = self._ctx
+        if ctx is None:
+            raise RuntimeError("ShardedEmbedding.push without a pull to answer (none yet, or ended by discard_pull)")
         kind = ctx[0] if isinstance(ctx[0], str) else None
         if kind == "fixed":
             self._push_fixed(grad_unique, scale)
@@ -820,6 +847,20 @@ class ShardedEmbedding:
         empty = torch.empty(0, dtype=torch.int64, device=self.device)
         self.pull(empty)
         self.push(torch.empty(0, self.dim, device=self.device), scale)
+
+    def discard_pull(self) -> None:
+        """End the last pull without a push (evaluation: rows were only read).  The
+        pull's context is dropped, so a stray ``push`` raises instead of writing
+        through stale slots.  A pull-only round is consistent on every exchange:
+        the fixed exchange's owner stamps are per call id (a later push reads
+        only its own pull's), and ``_agree`` reads the fills alone."""
+        self._ctx = None
+
+    def participate_pull(self) -> None:
+        """An owner without a batch of its own (PS rank) serves one pull-only round
+        (the workers' ``CTRModel.evaluate``): no row and no Adagrad state changes."""
+        self.pull(torch.empty(0, dtype=torch.int64, device=self.device))
+        self.discard_pull()
 
 
 # ---------------------------------------------------------------- model
@@ -911,3 +952,15 @@ class CTRModel:
             rows = xgrad[:, : self.F * self.D].reshape(B * self.F, self.D).float()
             g_u = torch.zeros(U, self.D, device=self.device).index_add_(0, inv, rows)
         self.emb.push(g_u, scale)
+
+    @torch.no_grad()
+    def evaluate(self, ids: torch.Tensor, dense: torch.Tensor, y: torch.Tensor, auc) -> torch.Tensor:
+        """Score one held-out batch: pull, forward-only tower, ``auc.update`` (a
+        ``StreamingAUC``), and the pull ended without a push -- no table row, no
+        Adagrad state and no parameter changes.  Returns the batch's mean BCE
+        loss (on the device; nothing here synchronises on the world-1 GPU path)."""
+        x, _inv, _U = self.build_input(ids, dense)
+        logit, loss = self.tower.logits(x, y)
+        auc.update(logit, y)
+        self.emb.discard_pull()
+        return loss

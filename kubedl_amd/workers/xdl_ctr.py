@@ -17,6 +17,13 @@ Without PS replicas the workers own the shards themselves.  Synthetic data:
 ``--vocab`` rows each, ``--dense`` dense features, labels from a hidden
 logistic model (so the loss visibly falls).  Prints one JSON line from the
 first worker: samples/s, steps/s, loss.
+
+``--eval-batches E`` scores E held-out batches per worker after the last step
+(and after every ``--eval-every`` steps): forward only, pulls without a push
+(PS ranks serve them with ``participate_pull``), a streaming AUC
+(``kubedl_amd.ops.auc``) merged over the workers, and the row-weighted log
+loss; the JSON line gains ``eval_*`` fields.  Evaluation time is kept out of
+the throughput figures.
 """
 from __future__ import annotations
 
@@ -50,6 +57,35 @@ def synth_batch(B, F, V, nd, gen, w_true):
     return ids, dense, y
 
 
+def eval_steps(total: int, eval_batches: int, eval_every: int):
+    """Steps (1-based, < total) after which the job evaluates inside the loop; with
+    ``eval_batches`` > 0 it always evaluates once more after step ``total``.  A
+    pure function of the job's arguments: every rank, PS included, derives the
+    same schedule."""
+    if eval_batches <= 0 or eval_every <= 0:
+        return frozenset()
+    return frozenset(range(eval_every, total, eval_every))
+
+
+def run_eval(model, batches, auc, wgroup, device) -> dict:
+    """Score the held-out ``batches`` (forward only, no push), merge the streaming
+    AUC state and the fp64 log-loss sums over the workers, and read them
+    (synchronises: call outside the timed region's accounting)."""
+    auc.reset()
+    acc = torch.zeros(2, dtype=torch.float64, device=device)  # (sum of batch loss x rows, rows)
+    for ids, dense, y in batches:
+        loss = model.evaluate(ids, dense, y, auc)
+        acc[0] += loss.double() * y.numel()
+        acc[1] += y.numel()
+    if wgroup is not None:
+        auc.merge(wgroup)
+        dist.all_reduce(acc, op=dist.ReduceOp.SUM, group=wgroup)
+    res = auc.compute()
+    loss_sum, rows = (float(v) for v in acc.tolist())
+    return {"auc": res["auc"], "logloss": loss_sum / rows if rows else float("nan"), "rows": int(rows),
+            "pos": res["pos"], "invalid": res["invalid"]}
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=None, help="default 50 (GPU) / 6 (CPU)")
@@ -66,6 +102,11 @@ def main(argv=None) -> int:
     ap.add_argument("--exchange", choices=("auto", "fixed"), default="auto",
                     help="fixed: the PS + worker fixed-capacity exchange even at world 1 (one-GPU rehearsal: "
                          "RCCL all-to-alls on a 1-rank group, one owner)")
+    ap.add_argument("--eval-batches", type=int, default=0,
+                    help="held-out batches per worker scored at every evaluation point (forward only, streaming "
+                         "AUC + log loss); 0: no evaluation")
+    ap.add_argument("--eval-every", type=int, default=0,
+                    help="also evaluate after every this many steps (warm-up included); 0: only after the last step")
     args, _unknown = ap.parse_known_args(argv)
     # the BASELINE.json config on the GPU; a plumbing-sized job on CPU (the
     # reference's example specs carry no sizes, so they run with these)
@@ -120,9 +161,16 @@ def main(argv=None) -> int:
                            group=None, lr=args.emb_lr, max_ids=args.batch * args.fields,
                            force_fixed=args.exchange == "fixed", rows_bf16=True)
     total = args.warmup + args.steps
-    if not is_worker:  # PS: serve pull/push rounds
-        for _ in range(total):
+    E = max(args.eval_batches, 0)
+    mid_evals = eval_steps(total, E, args.eval_every)
+    if not is_worker:  # PS: serve pull/push rounds (and the evaluations' pull-only rounds)
+        for it in range(total):
             emb.participate(scale=1.0 / len(workers))  # the workers' push scale
+            if it + 1 in mid_evals:
+                for _ in range(E):
+                    emb.participate_pull()
+        for _ in range(E):  # the evaluation after the last step
+            emb.participate_pull()
         emb.finalize()
         dist.barrier()
         dist.destroy_process_group()
@@ -140,6 +188,15 @@ def main(argv=None) -> int:
     # every step's synthetic batch is generated on the device before the timed
     # loop (distinct batches, no host work or H2D copy inside the timed steps)
     batches = [synth_batch(args.batch, args.fields, args.vocab, args.dense, gen, w_true) for _ in range(total)]
+    # held-out batches from a generator of their own (the training batches'
+    # random stream is the same with and without evaluation)
+    eval_set, auc, history = [], None, []
+    if E > 0:
+        from kubedl_amd.ops.auc import StreamingAUC
+        egen = torch.Generator(device=device).manual_seed(9000 + rank)
+        eval_set = [synth_batch(args.batch, args.fields, args.vocab, args.dense, egen, w_true) for _ in range(E)]
+        auc = StreamingAUC(device)
+    eval_s = 0.0  # time of the in-loop evaluations inside the timed region (subtracted below)
     losses = []
     t0 = None
     for it in range(total):
@@ -163,12 +220,33 @@ def main(argv=None) -> int:
         ddp.finish()
         opt.step()
         losses.append(loss.detach())
-        common.report_progress(it + 1, final=it + 1 == total)
+        common.report_progress(it + 1, final=it + 1 == total and E == 0)
+        if it + 1 in mid_evals:
+            # an evaluation point inside the loop: drained before and after, its
+            # time taken out of the timed region's accounting
+            if use_gpu:
+                torch.cuda.synchronize()
+            te = time.perf_counter()
+            ev = run_eval(model, eval_set, auc, wgroup, device)
+            history.append({"step": it + 1, "auc": ev["auc"], "logloss": ev["logloss"]})
+            if use_gpu:
+                torch.cuda.synchronize()
+            if t0 is not None and it >= args.warmup:
+                eval_s += time.perf_counter() - te
     # host time to issue the timed steps (no sync inside the loop): ~dt when host-bound
-    issue = time.perf_counter() - t0 if t0 is not None else 0.0
+    issue = time.perf_counter() - t0 - eval_s if t0 is not None else 0.0
     if use_gpu:
         torch.cuda.synchronize()
-    dt = time.perf_counter() - t0 if t0 is not None else 0.0
+    dt = time.perf_counter() - t0 - eval_s if t0 is not None else 0.0
+    estats = {}
+    if E > 0:  # the evaluation after the last step: after dt is taken
+        ev = run_eval(model, eval_set, auc, wgroup, device)
+        estats = {"eval_auc": ev["auc"], "eval_logloss": ev["logloss"], "eval_rows": ev["rows"],
+                  "eval_pos": ev["pos"], "eval_invalid": ev["invalid"]}
+        if args.eval_every > 0:
+            history.append({"step": total, "auc": ev["auc"], "logloss": ev["logloss"]})
+            estats["eval_history"] = history
+        common.report_progress(total, final=True, auc=ev["auc"])
     xstats = emb.finalize()  # (after the timed region: reads the last exchanges' agreed fills)
     if world > 1:
         t = torch.tensor([dt], device=device)
@@ -184,7 +262,7 @@ def main(argv=None) -> int:
                           "samples_per_sec": args.steps * args.batch * len(workers) / dt if dt > 0 else 0.0,
                           "loss_first": first, "loss_last": last, "device": str(device),
                           "hip_kernels": emb.use_hip, "exchange": "fixed" if emb._fixed() else "sync-free",
-                          **xstats}), flush=True)
+                          **xstats, **estats}), flush=True)
     if world > 1 or rehearse:
         dist.barrier()
         dist.destroy_process_group()
