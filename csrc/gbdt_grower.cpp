@@ -274,6 +274,31 @@ class GbdtGrower {
   // look-backs of the fused route + scan that timed out (syncs; expected 0)
   int64_t scan_faults() const { return scan_fault_.item<int>(); }
   int64_t rows_per_chunk() const { return rpb_; }
+  // Test hook (tests/test_gbdt_grower.py): the grower's own tensors as they are now, level d's
+  // segments among them -- no copy, no launch, no synchronisation.  rows / node_pos / hist_cur
+  // swap buffers every level and level_c zeroes built, so a caller clones what it wants to keep
+  // and asks again after each step.
+  pybind11::dict debug_state(int64_t d) const {
+    TORCH_CHECK(d >= 0 && d <= D_, "GbdtGrower.debug_state: 0 <= d <= max_depth");
+    pybind11::dict s;
+    s["rows"] = rows_;
+    s["node_pos"] = node_pos_;
+    s["lo"] = lo_[d];
+    s["hi"] = hi_[d];
+    s["exists"] = exists_[d];
+    s["split"] = split_;
+    s["gain"] = gain_;
+    s["sbin"] = sbin_;
+    s["tot"] = tot_;
+    s["hist_cur"] = hist_cur_;
+    s["built"] = built_;
+    s["cnt"] = cnt_;
+    s["build_child"] = build_child_;
+    s["blo"] = blo_;
+    s["bhi"] = bhi_;
+    s["gh_max"] = gh_max_;
+    return s;
+  }
 
  private:
   at::Tensor bins_, bins_t_, cuts_, grad_, hess_;
@@ -422,6 +447,8 @@ void register_gbdt(pybind11::module& m) {
       .def("stats", &GbdtGrower::stats)
       .def("rows_per_chunk", &GbdtGrower::rows_per_chunk)
       .def("scan_faults", &GbdtGrower::scan_faults)
+      .def("debug_state", &GbdtGrower::debug_state, py::arg("d"),
+           "test hook: the grower's own tensors (level d's lo / hi / exists), no copy and no launch")
       .def_static("set_route_plan", [](int v) { GbdtGrower::g_route_plan = v; },
                   "1: the three-launch level (route + counts, plan, partition), 0: route / scan / partition / "
                   "children, -1: KDL_TUNE gbdt_route_plan")
