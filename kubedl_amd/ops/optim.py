@@ -304,8 +304,11 @@ class FusedSGD(_FusedBase):
         sp.pack_grads()
         first = self.step_count == 0
         if self._use_hip():
+            # without momentum there is no buffer for dampening to act on (torch.optim.SGD ignores it):
+            # the kernel's bk = 0*b + (1 - dampening)*gk would scale the whole update instead
+            dampening = self.dampening if self.momentum != 0 else 0.0
             _ext.load().sgd_step(sp.chunks, sp.master, self.mom, sp.grad, sp.param, float(self.lr),
-                                 float(self.momentum), float(self.dampening), float(self.grad_scale),
+                                 float(self.momentum), float(dampening), float(self.grad_scale),
                                  bool(self.nesterov), bool(first), [float(self.weight_decay), 0.0],
                                  [1.0, 1.0])
         else:
