@@ -1098,6 +1098,40 @@ void head_forward(const at::Tensor& x, const at::Tensor& w, const c10::optional<
             "head_forward");
 }
 
+// evaluation: loss_row fp32 [Nb], rank_row int32 [Nb], optional logits fp32 [Nb, L],
+// totals fp64 [4] += (loss sum, top-1 hits, top-5 hits, images); any Nb
+void head_eval(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& b, const at::Tensor& y,
+               at::Tensor feat, at::Tensor part1, at::Tensor loss_row, at::Tensor rank_row,
+               const c10::optional<at::Tensor>& logits, at::Tensor totals) {
+  TORCH_CHECK(x.dim() == 4 && is_nhwc_dense(x), "head_eval: x must be [Nb, C, H, W] channels_last");
+  const int64_t Nb = x.size(0), C = x.size(1), HW = x.size(2) * x.size(3);
+  TORCH_CHECK(w.dim() == 2 && w.size(1) == C && w.is_contiguous(), "head_eval: w must be [L, C] contiguous");
+  const int64_t L = w.size(0);
+  TORCH_CHECK(Nb > 0 && C % 8 == 0 && L <= 8192, "head_eval: C % 8 == 0, L <= 8192");
+  need_bf16(x, Nb * C * HW, "head x");
+  need_bf16(w, L * C, "head w");
+  need_opt_bf16(b, L, "head b");
+  TORCH_CHECK(!b.has_value() || !b->defined() || b->is_contiguous(), "head b: contiguous");
+  TORCH_CHECK(y.is_cuda() && y.scalar_type() == at::kLong && y.is_contiguous() && y.numel() == Nb, "head y: int64 [Nb]");
+  auto sp = head_splits(Nb, C, L);
+  need_bf16(feat, Nb * C, "head feat");
+  need_f32(part1, sp[0] * Nb * L, "head part1");
+  need_f32(loss_row, Nb, "head loss_row");
+  TORCH_CHECK(rank_row.is_cuda() && rank_row.scalar_type() == at::kInt && rank_row.is_contiguous() &&
+                  rank_row.numel() >= Nb,
+              "head rank_row: int32 [Nb]");
+  need_opt_f32(logits, Nb * L, "head logits");
+  TORCH_CHECK(totals.is_cuda() && totals.scalar_type() == at::kDouble && totals.is_contiguous() &&
+                  totals.numel() >= 4,
+              "head totals: fp64 [4]");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
+  check_hip(kdl::head_eval(x.data_ptr(), static_cast<int>(Nb), static_cast<int>(HW), static_cast<int>(C),
+                           w.data_ptr(), opt_ptr(b), static_cast<int>(L), y.data_ptr<int64_t>(), feat.data_ptr(),
+                           part1.data_ptr<float>(), loss_row.data_ptr<float>(), rank_row.data_ptr<int32_t>(),
+                           opt_fptr(logits), totals.data_ptr<double>(), cur_stream()),
+            "head_eval");
+}
+
 void head_backward(const at::Tensor& feat, const at::Tensor& w, const at::Tensor& dl, const at::Tensor& dlT,
                    at::Tensor part2, at::Tensor dfeat, at::Tensor dW, at::Tensor db, const at::Tensor& lrow,
                    at::Tensor loss) {
@@ -1441,6 +1475,151 @@ void conv3x3_gemm(const at::Tensor& A, const at::Tensor& W, at::Tensor C, int64_
   a.aout = aout;
   apply_fin_arm(fin, a, N, epi);
   check_hip(kdl::conv1x1_gemm(a, cur_stream()), "conv3x3_gemm");
+}
+
+// Inference convs: the BatchNorm that follows is the fixed per-channel transform
+// coef = [scale | shift] (bn_infer_coefs), folded with the ReLU and the block's
+// identity into the GEMM epilogue (csrc/gemm_epi.h EPI_BN / BN_RELU / BN_RES_RELU):
+//   C = bf16([relu](fmaf(conv, scale, shift) [+ res]))
+// No statistics, no prologue.  An arming left pending by a training call
+// (bn_fin_arm, bn_bwd_pro_arm / bn_res_pro_arm, conv3x3_aout_arm) is consumed
+// and refused here, so it can never reach the next training GEMM.
+void refuse_arms(const char* who) {
+  const FinArm fin = take_fin_arm();
+  const BwdArm bw = take_bwd_arm();
+  void* aout = g_aout_arm;
+  g_aout_arm = nullptr;
+  g_aout_n = 0;
+  TORCH_CHECK(!fin.ws, who, ": a bn_fin_arm is pending (inference convs finalize nothing); it has been cleared");
+  TORCH_CHECK(!bw.x, who, ": a bn_bwd_pro_arm / bn_res_pro_arm is pending (inference convs have no prologue); "
+              "it has been cleared");
+  TORCH_CHECK(!aout, who, ": a conv3x3_aout_arm is pending (inference convs write nothing through); "
+              "it has been cleared");
+}
+
+void conv1x1_bn(const at::Tensor& A, const at::Tensor& W, at::Tensor C, int64_t M, int64_t N, int64_t K,
+                int64_t Hout, int64_t Wout, int64_t Hin, int64_t Win, int64_t stride, const at::Tensor& coef,
+                bool relu, const c10::optional<at::Tensor>& res) {
+  refuse_arms("conv1x1_bn");
+  TORCH_CHECK(K % 64 == 0 && N % 64 == 0 && M > 0 && stride >= 1, "conv1x1_bn: need K % 64 == 0, N % 64 == 0");
+  const bool has_res = opt_ptr(res) != nullptr;
+  TORCH_CHECK(!has_res || (relu && stride == 1), "conv1x1_bn: res needs relu and stride 1");
+  const int64_t rows_in = stride > 1 ? (M / (Hout * Wout)) * Hin * Win : M;
+  if (stride > 1) TORCH_CHECK(Hout > 0 && Wout > 0 && M % (Hout * Wout) == 0 && (Hout - 1) * stride < Hin &&
+                                  (Wout - 1) * stride < Win,
+                              "conv1x1_bn: gather geometry");
+  need_bf16(A, rows_in * K, "conv1x1_bn A");
+  need_bf16(W, N * K, "conv1x1_bn W");
+  need_bf16(C, M * N, "conv1x1_bn C");
+  need_f32(coef, 2 * N, "conv1x1_bn coef");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(coef.data_ptr()) % 8 == 0, "conv1x1_bn coef: 8-byte aligned");
+  need_opt_bf16(res, M * N, "conv1x1_bn res");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(A.device());
+  kdl::Conv1x1Args a{};
+  a.A = A.data_ptr(); a.B = W.data_ptr(); a.C = C.data_ptr();
+  a.M = static_cast<int>(M); a.N = static_cast<int>(N); a.K = static_cast<int>(K);
+  a.Hout = static_cast<int>(Hout); a.Wout = static_cast<int>(Wout); a.Hin = static_cast<int>(Hin);
+  a.Win = static_cast<int>(Win); a.stride = static_cast<int>(stride);
+  a.epi = has_res ? 9 : relu ? 8 : 7;
+  a.ecoef = coef.data_ptr<float>();
+  a.eres = opt_ptr(res);
+  a.res_stride = 1;
+  check_hip(kdl::conv1x1_gemm(a, cur_stream()), "conv1x1_bn");
+}
+
+void conv3x3_bn(const at::Tensor& A, const at::Tensor& W, at::Tensor C, int64_t Nb, int64_t H, int64_t Wd,
+                int64_t Cin, int64_t Cout, int64_t stride, const at::Tensor& coef, bool relu) {
+  refuse_arms("conv3x3_bn");
+  TORCH_CHECK(Cin % 64 == 0 && Cout % 64 == 0 && Nb > 0 && stride >= 1 && H > 0 && Wd > 0,
+              "conv3x3_bn: need Cin, Cout % 64 == 0");
+  TORCH_CHECK(relu, "conv3x3_bn: the 3x3 convs are served with the BN + ReLU epilogue only");
+  const int64_t Ho = (H - 1) / stride + 1, Wo = (Wd - 1) / stride + 1;
+  const int64_t M = Nb * Ho * Wo, K = 9 * Cin, N = Cout;
+  need_bf16(A, Nb * H * Wd * Cin, "conv3x3_bn A");
+  need_bf16(W, N * K, "conv3x3_bn W");
+  need_bf16(C, M * N, "conv3x3_bn C");
+  need_f32(coef, 2 * N, "conv3x3_bn coef");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(coef.data_ptr()) % 8 == 0, "conv3x3_bn coef: 8-byte aligned");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(A.device());
+  kdl::Conv1x1Args a{};
+  a.A = A.data_ptr(); a.B = W.data_ptr(); a.C = C.data_ptr();
+  a.M = static_cast<int>(M); a.N = static_cast<int>(N); a.K = static_cast<int>(K);
+  a.Hout = static_cast<int>(Ho); a.Wout = static_cast<int>(Wo); a.Hin = static_cast<int>(H);
+  a.Win = static_cast<int>(Wd); a.stride = static_cast<int>(stride);
+  a.ksize = 3; a.Cin = static_cast<int>(Cin);
+  a.epi = 8;
+  a.ecoef = coef.data_ptr<float>();
+  a.res_stride = 1;
+  check_hip(kdl::conv1x1_gemm(a, cur_stream()), "conv3x3_bn");
+}
+
+std::vector<int64_t> gemm_last_launch() {
+  int core = -1, cfg = -1;
+  kdl::gemm_last_launch(&core, &cfg);
+  return {core, cfg};
+}
+
+// (table, floats): the device pointer table of bn_infer_coefs for these BN
+// layers -- one (gamma, beta, running_mean, running_var) tuple each, gamma / beta
+// fp32 or bf16 (one dtype per layer) or None -- and the size of the flat
+// coefficient buffer; layer i's [2 C_i] scale | shift slice starts at
+// table[i, 5] floats, 16-byte aligned.
+py::tuple bn_infer_table(const std::vector<std::vector<c10::optional<at::Tensor>>>& layers) {
+  static_assert(sizeof(kdl::BnInferRow) == 48, "BnInferRow layout");
+  TORCH_CHECK(!layers.empty(), "bn_infer_table: no layers");
+  std::vector<kdl::BnInferRow> rows(layers.size());
+  int64_t off = 0;
+  at::Device dev(at::kCPU);
+  for (size_t i = 0; i < layers.size(); ++i) {
+    const auto& l = layers[i];
+    TORCH_CHECK(l.size() == 4 && l[2].has_value() && l[3].has_value(),
+                "bn_infer_table: (gamma, beta, running_mean, running_var) per layer");
+    const at::Tensor& rm = *l[2];
+    const at::Tensor& rv = *l[3];
+    const int64_t C = rm.numel();
+    TORCH_CHECK(C > 0 && C < (int64_t(1) << 30), "bn_infer_table: channel count");
+    need_f32(rm, C, "bn_infer_table running_mean");
+    need_f32(rv, C, "bn_infer_table running_var");
+    TORCH_CHECK(rv.numel() == C, "bn_infer_table: running_var size");
+    if (i == 0) dev = rm.device();
+    TORCH_CHECK(rm.device() == dev && rv.device() == dev, "bn_infer_table: one device");
+    int pt = -1;
+    for (int j = 0; j < 2; ++j) {
+      if (!l[j].has_value() || !l[j]->defined()) continue;
+      const at::Tensor& t = *l[j];
+      TORCH_CHECK(t.is_cuda() && t.device() == dev && t.is_contiguous() && t.numel() == C,
+                  "bn_infer_table: affine tensors [C] on the statistics' device");
+      const int this_pt = dtype_code(t);
+      TORCH_CHECK(pt < 0 || pt == this_pt, "bn_infer_table: affine tensors of one dtype");
+      pt = this_pt;
+    }
+    kdl::BnInferRow& r = rows[i];
+    r.gamma = opt_ptr(l[0]);
+    r.beta = opt_ptr(l[1]);
+    r.mean = rm.data_ptr<float>();
+    r.var = rv.data_ptr<float>();
+    r.C = static_cast<int32_t>(C);
+    r.pt_bf16 = pt == 1 ? 1 : 0;
+    r.off = off;
+    off += (2 * C + 3) / 4 * 4;
+  }
+  auto host = at::empty({static_cast<int64_t>(rows.size()), 6}, at::TensorOptions().dtype(at::kLong));
+  std::memcpy(host.data_ptr<int64_t>(), rows.data(), rows.size() * sizeof(kdl::BnInferRow));
+  return py::make_tuple(host.to(dev), off);
+}
+
+void bn_infer_coefs(const at::Tensor& table, at::Tensor out, double eps) {
+  TORCH_CHECK(table.is_cuda() && table.scalar_type() == at::kLong && table.dim() == 2 && table.size(1) == 6 &&
+                  table.is_contiguous(),
+              "bn_infer_coefs: table must be the int64 [n, 6] GPU tensor of bn_infer_table");
+  need_f32(out, 1, "bn_infer_coefs out");
+  TORCH_CHECK(out.device() == table.device() && reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0,
+              "bn_infer_coefs out: 16-byte aligned, on the table's device");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(table.device());
+  check_hip(kdl::bn_infer_coefs(reinterpret_cast<const kdl::BnInferRow*>(table.data_ptr<int64_t>()),
+                                static_cast<int>(table.size(0)), static_cast<float>(eps), out.data_ptr<float>(),
+                                out.numel(), cur_stream()),
+            "bn_infer_coefs");
 }
 
 // ResNet stem 7x7 / stride 2 / pad 3 conv, [Nb, 3, H, W] -> [Nb, 64, OH, OW] (csrc/stem.hip).
@@ -1951,6 +2130,12 @@ PYBIND11_MODULE(_C, m) {
         py::arg("Hx") = 0, py::arg("Wx") = 0);
   m.def("bn_res_pro_arm", &bn_res_pro_arm, "next forward conv1x1_gemm applies relu(A*scale+shift+res), written through + mask");
   m.def("conv3x3_aout_arm", &conv3x3_aout_arm, "next prologue conv3x3_gemm also writes relu(B(x)) here (56x56 halo)");
+  m.def("conv1x1_bn", &conv1x1_bn, "inference 1x1 conv: BN (scale | shift) [+ identity] [+ ReLU] in the GEMM epilogue");
+  m.def("conv3x3_bn", &conv3x3_bn, "inference 3x3 pad-1 conv: BN (scale | shift) + ReLU in the GEMM epilogue");
+  m.def("gemm_last_launch", &gemm_last_launch, "(main loop, tile config) of the last inference-epilogue conv GEMM");
+  m.def("bn_infer_table", &bn_infer_table, "pointer table + buffer size for bn_infer_coefs");
+  m.def("bn_infer_coefs", &bn_infer_coefs, "scale | shift of every BN of a network from its running statistics, one launch");
+  m.def("head_eval", &head_eval, "classifier head evaluation: pool + fc + per-image loss and label rank + fp64 totals");
   m.def("conv3x3_gemm", &conv3x3_gemm, "3x3 pad-1 conv (fwd or stride-1 dgrad) as implicit MFMA GEMM with fused BN prologue/epilogue");
   m.def("conv1x1_wgrad", &conv1x1_wgrad, "1x1 conv weight gradient (split-M MFMA into fp32 slabs, fixed-order reduce + bf16 cast); solo: no side stream shares the GPU (more splits)",
         py::arg("G"), py::arg("A"), py::arg("pro_coef"), py::arg("dw32"), py::arg("dW"), py::arg("scale"), py::arg("M"),

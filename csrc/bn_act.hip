@@ -1171,4 +1171,42 @@ hipError_t bn_stage_bwd_apply(const void* g, const void* x, const float* ws, voi
   return hipGetLastError();
 }
 
+
+// ---------------------------------------------------------------- inference coefficients
+// Every BatchNorm of a network in one launch (a pointer table, as
+// csrc/multi_tensor.hip's): block i turns row i = (gamma, beta, running_mean,
+// running_var, C, affine dtype, offset) into the fixed per-channel transform
+//   scale = gamma * rsqrt(var + eps),  shift = beta - mean * scale
+// at out[off : off + 2C] = scale | shift -- the ``ecoef`` table of the conv
+// GEMMs' inference epilogues (csrc/gemm_epi.h EPI_BN*).  A row whose slice
+// would end past ``out_floats`` writes nothing.
+namespace {
+__global__ __launch_bounds__(256) void bn_infer_coefs_kernel(const BnInferRow* __restrict__ rows, float eps,
+                                                             float* __restrict__ out, int64_t out_floats) {
+  const BnInferRow r = rows[blockIdx.x];
+  if (r.C <= 0 || r.off < 0 || r.off + 2 * static_cast<int64_t>(r.C) > out_floats) return;
+  float* o = out + r.off;
+  for (int c = threadIdx.x; c < r.C; c += 256) {
+    float g = 1.f, b = 0.f;
+    if (r.pt_bf16) {
+      if (r.gamma) g = ldp<bf16_t>(static_cast<const bf16_t*>(r.gamma), c);
+      if (r.beta) b = ldp<bf16_t>(static_cast<const bf16_t*>(r.beta), c);
+    } else {
+      if (r.gamma) g = ldp<float>(static_cast<const float*>(r.gamma), c);
+      if (r.beta) b = ldp<float>(static_cast<const float*>(r.beta), c);
+    }
+    const float sc = g * rsqrtf(r.var[c] + eps);
+    o[c] = sc;
+    o[r.C + c] = b - r.mean[c] * sc;
+  }
+}
+}  // namespace
+
+hipError_t bn_infer_coefs(const BnInferRow* rows, int nrows, float eps, float* out, int64_t out_floats,
+                          hipStream_t s) {
+  if (nrows <= 0) return hipSuccess;
+  hipLaunchKernelGGL(bn_infer_coefs_kernel, dim3(nrows), dim3(256), 0, s, rows, eps, out, out_floats);
+  return hipGetLastError();
+}
+
 }  // namespace kdl

@@ -706,6 +706,17 @@ hipError_t dispatch_epi(const GemmParams& p, int epi, hipStream_t s) {
     if constexpr (PRO == PRO_NONE && GATHER == G_CONV3) {
       if (epi == EPI_MASKX) return launch_gemm<BM, BN, MINB, PRO, GATHER, EPI_MASKX, KBK>(p, s);
     }
+    // inference epilogues (BN folded into the conv): the 128-row, 64-deep-K tiles only
+    // (infer_config routes every forced config to one of them)
+    if constexpr (PRO == PRO_NONE && BM == 128 && MINB == 2 && KBK == BK) {
+      if constexpr (GATHER == G_DENSE || GATHER == G_STRIDED) {
+        if (epi == EPI_BN) return launch_gemm<BM, BN, MINB, PRO, GATHER, EPI_BN, KBK>(p, s);
+      }
+      if (epi == EPI_BN_RELU) return launch_gemm<BM, BN, MINB, PRO, GATHER, EPI_BN_RELU, KBK>(p, s);
+      if constexpr (GATHER == G_DENSE) {
+        if (epi == EPI_BN_RES_RELU) return launch_gemm<BM, BN, MINB, PRO, GATHER, EPI_BN_RES_RELU, KBK>(p, s);
+      }
+    }
     return hipErrorInvalidValue;
   }
 }
@@ -752,6 +763,11 @@ namespace {
 int g_core = tune_int("gemm_core", -1);
 }  // namespace
 
+// main loop and tile config of the last inference-epilogue launch on this thread (tests):
+// core 0 register-staged (cfg 0 = 128x128, 1 = 128x64), 1 LDS-DMA (cfg = csrc/igemm.hip's)
+thread_local int g_last_core = -1, g_last_cfg = -1;
+void gemm_last_launch(int* core, int* cfg) { *core = g_last_core; *cfg = g_last_cfg; }
+
 int gemm_core_mode() { return g_core; }
 void set_gemm_core_mode(int m) { g_core = m; }
 
@@ -779,7 +795,14 @@ hipError_t conv1x1_gemm(const Conv1x1Args& a, hipStream_t s) {
   if (bpro && a.bres && (!a.bcoef || a.pro_coef || a.stride > 1 || a.ksize == 3 || a.epi != EPI_STATS ||
                          !a.aout || !a.obits || a.K > bwd_kmax(64)))
     return hipErrorInvalidValue;
-  if (a.epi != EPI_PLAIN && a.epi != EPI_STATS && a.epi != EPI_MASKX && a.epi != EPI_RESBITS && a.epi != EPI_RES)
+  const bool infer = a.epi == EPI_BN || a.epi == EPI_BN_RELU || a.epi == EPI_BN_RES_RELU;
+  if (a.epi != EPI_PLAIN && a.epi != EPI_STATS && a.epi != EPI_MASKX && a.epi != EPI_RESBITS && a.epi != EPI_RES &&
+      !infer)
+    return hipErrorInvalidValue;
+  // inference epilogues: scale | shift in ecoef, no prologue, no finalize, a dense identity
+  if (infer && (!a.ecoef || a.pro_coef || bpro || a.fin_ws || a.aout ||
+                (a.epi == EPI_BN_RES_RELU && (!a.eres || p.res_stride != 1 || a.stride > 1 || a.ksize == 3)) ||
+                (a.ksize == 3 && a.epi != EPI_BN_RELU)))
     return hipErrorInvalidValue;
   const int pro = bpro ? (a.bres == 2 ? PRO_RES2 : a.bres ? PRO_RES : PRO_BWD)
                 : a.pro_coef != nullptr ? PRO_FWD : PRO_NONE;
@@ -823,8 +846,13 @@ hipError_t conv1x1_gemm(const Conv1x1Args& a, hipStream_t s) {
     // 3x3 at N = 512 (7x7 stage): 256x128 tiles (1 block/CU) beat 128x128 by 2-3 %
     // (86.5-88.5 vs 89-90.6 us, profiles/r02_halo3x3_vs_igemm.jsonl dma1 vs dma2)
     if (gather == G_CONV3 && p.N == 512 && g_forced_cfg_unset()) cfg = 1;
+    if (infer) cfg = igemm_infer_cfg(cfg, epi, p.N);
     const hipError_t e = igemm(p, epi, gather, cfg, s);
-    if (e != hipErrorInvalidValue) return e;
+    if (e != hipErrorInvalidValue) {
+      g_last_core = 1;
+      g_last_cfg = infer ? cfg : -1;
+      return e;
+    }
   }
   if (pro == PRO_RES2) {  // four coefficient rows; 128 x 64 tiles (128 x 128 spills 12 B)
     if (4 * p.K <= 3 * bwd_kmax(64)) return dispatch_pg<128, 64, 2>(p, epi, pro, gather, s);
@@ -835,6 +863,13 @@ hipError_t conv1x1_gemm(const Conv1x1Args& a, hipStream_t s) {
     if (p.K <= bwd_kmax(64)) return dispatch_pg<128, 64, 2>(p, epi, pro, gather, s);
     return hipErrorInvalidValue;
   }
+  g_last_core = 0;
+  if (infer) {  // instantiated on the 128x128 and 128x64 tiles only: every forced config lands on one of them
+    g_last_cfg = p.N % 128 == 0 ? 0 : 1;
+    return g_last_cfg == 0 ? dispatch_pg<128, 128, 2>(p, epi, pro, gather, s)
+                           : dispatch_pg<128, 64, 2>(p, epi, pro, gather, s);
+  }
+  g_last_cfg = -1;
   switch (pick_config(p.M, p.N, p.K, epi)) {
     case 0: return dispatch_pg<128, 128, 2>(p, epi, pro, gather, s);
     case 1: return dispatch_pg<128, 64, 2>(p, epi, pro, gather, s);

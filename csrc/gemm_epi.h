@@ -19,6 +19,12 @@
 //   BIAS / BIAS_RELU  y = [relu](c + bias[n]) (the CTR tower's dense layers,
 //            csrc/ctr.hip gemm_bias_act; bias fp32 in ``shift`` or bf16 in
 //            ``bias16``; c is the bf16-rounded accumulator)
+//   BN / BN_RELU / BN_RES_RELU  inference: the BatchNorm that follows the conv
+//            is a fixed per-channel scale | shift (``ecoef`` [2N], from the
+//            running statistics), y = [relu](fmaf(c, scale, shift) [+ res]) with
+//            one rounding to bf16 -- the arithmetic of bn_fwd_apply_kernel
+//            (csrc/bn_act.hip), so the store is bit-identical to PLAIN followed
+//            by that pass; res = a dense [M, N] tensor in ``eres``.  No sums.
 // and after its last tile folds the per-thread sums in LDS and adds them to
 // the BN workspace replica of the block (one atomic per channel per block).
 #pragma once
@@ -36,7 +42,8 @@ typedef __attribute__((ext_vector_type(2))) float f2_t;
 
 constexpr int kRep = 32;  // replica count of the BN workspace (== bn_act.hip kReplicas)
 
-enum { EPI_PLAIN = 0, EPI_STATS = 1, EPI_MASKX = 2, EPI_RESBITS = 3, EPI_RES = 4, EPI_BIAS = 5, EPI_BIAS_RELU = 6 };
+enum { EPI_PLAIN = 0, EPI_STATS = 1, EPI_MASKX = 2, EPI_RESBITS = 3, EPI_RES = 4, EPI_BIAS = 5, EPI_BIAS_RELU = 6,
+       EPI_BN = 7, EPI_BN_RELU = 8, EPI_BN_RES_RELU = 9 };
 // A-row addressing: dense rows | stride-s 1x1 gather | 3x3 implicit GEMM (pad 1, stride s) |
 // data gradient of a stride-2 3x3 pad-1 conv as four sub-pixel class GEMMs (csrc/igemm.hip)
 // G_STEM (csrc/stem.hip): a tile is 2 output rows x 112 columns of one image
@@ -69,8 +76,8 @@ struct GemmParams {
   float* acc;           // STATS/MASKX/RESBITS: [kRep][2N]
   const bf16_t* ex;     // MASKX/RESBITS: BN input x [M, N]
   const float* emean;   // [N]
-  const float* ecoef;   // MASKX: [2N] forward scale | shift of that BN
-  const bf16_t* eres;   // RESBITS/RES: d(identity)
+  const float* ecoef;   // MASKX: [2N] forward scale | shift of that BN; BN*: [2N] inference scale | shift
+  const bf16_t* eres;   // RESBITS/RES: d(identity); BN_RES_RELU: the block's identity [M, N]
   int res_stride;       // 1: eres is [M, N]; s > 1: eres is [Nb, Hin/s.., N] sampled at (h%s==0, w%s==0)
   int res_H, res_W;     // geometry of the C rows (= input resolution) for the strided residual
   const uint8_t* ebits; // RESBITS: [M, N/8]
@@ -118,6 +125,7 @@ hipError_t wgrad_dma(const WgParams& p, int nsplit, int tn, int tk, hipStream_t 
 int igemm_pick(int M, int N, int K);
 bool g_forced_cfg_unset();  // no KDL_TUNE igemm_cfg / set_igemm_cfg override in force
 hipError_t igemm(const GemmParams& p, int epi, int gather, int cfg, hipStream_t s);
+int igemm_infer_cfg(int cfg, int epi, int N);  // the config that serves an inference epilogue (EPI_BN*) under ``cfg``
 // n zeroed ticket counters for one launch, from a per-device ring (self-resetting:
 // every kernel that draws from them leaves them zero); null while a stream capture
 // is under way on a device whose ring does not exist yet
@@ -194,7 +202,8 @@ struct Epilogue {
   static constexpr int PG = (EPI == EPI_RESBITS || (EPI == EPI_MASKX && BM * BN >= 256 * 256))
                                 ? (NP > 4 ? 4 : NP) : (NP > 8 ? 8 : NP);
   static constexpr bool LX = EPI == EPI_MASKX || EPI == EPI_RESBITS;  // the BN input x
-  static constexpr bool LR = EPI == EPI_RESBITS || EPI == EPI_RES;
+  static constexpr bool LR = EPI == EPI_RESBITS || EPI == EPI_RES || EPI == EPI_BN_RES_RELU;
+  static constexpr bool BNI = EPI == EPI_BN || EPI == EPI_BN_RELU || EPI == EPI_BN_RES_RELU;  // inference BN
   // RESBITS' optional second BN input (downsample branch)
   static constexpr bool X2 = EPI == EPI_RESBITS;
   static constexpr bool REDUCE = EPI == EPI_STATS || EPI == EPI_MASKX || EPI == EPI_RESBITS;
@@ -320,6 +329,12 @@ struct Epilogue {
 #pragma unroll
         for (int q = 0; q < 4; ++q) ea[q] = b[q];
       }
+    } else if constexpr (BNI) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        ea[q] = ld2(p.ecoef, ch0 + 2 * q);
+        eb[q] = ld2(p.ecoef, N + ch0 + 2 * q);
+      }
     }
   }
 
@@ -376,6 +391,18 @@ struct Epilogue {
             for (int q = 0; q < 4; ++q) {
               f2_t y = v[q] + ea[q];
               if constexpr (EPI == EPI_BIAS_RELU) y = f2_t{y.x > 0.f ? y.x : 0.f, y.y > 0.f ? y.y : 0.f};
+              o[q] = pack2(y);
+            }
+            out = make_uint4(o[0], o[1], o[2], o[3]);
+          } else if constexpr (BNI) {  // o = fmaf(c, scale, shift); o += res; relu; one rounding
+            f2_t r[4];
+            (void)r;
+            if constexpr (EPI == EPI_BN_RES_RELU) unpack4x2(crv[i], r);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+              f2_t y = pfma(v[q], ea[q], eb[q]);
+              if constexpr (EPI == EPI_BN_RES_RELU) y += r[q];
+              if constexpr (EPI != EPI_BN) y = f2_t{y.x > 0.f ? y.x : 0.f, y.y > 0.f ? y.y : 0.f};
               o[q] = pack2(y);
             }
             out = make_uint4(o[0], o[1], o[2], o[3]);

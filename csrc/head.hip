@@ -256,6 +256,60 @@ __global__ __launch_bounds__(256) void head_ce_kernel(const float* __restrict__ 
   }
 }
 
+// Evaluation: head_ce_kernel without the gradient.  Block n: the same z and
+// loss_n (same expressions, same split order: bit-equal to head_ce_kernel's
+// lrow), the label's rank under the tie rule "equal logits at a lower index
+// come first", optionally the fp32 logits.
+__global__ __launch_bounds__(256) void head_eval_kernel(const float* __restrict__ part1, int splits, int Nb, int L,
+                                                        const bf16_t* __restrict__ bias,
+                                                        const int64_t* __restrict__ y, float* __restrict__ lrow,
+                                                        int32_t* __restrict__ rank, float* __restrict__ logits) {
+  extern __shared__ float z[];  // [L]
+  __shared__ float red[4];
+  const int n = blockIdx.x, t = threadIdx.x;
+  float mx = -INFINITY;
+  for (int l = t; l < L; l += 256) {
+    float v = bias ? bf16_to_f32(bias[l]) : 0.f;
+    for (int s = 0; s < splits; ++s) v += part1[(static_cast<int64_t>(s) * Nb + n) * L + l];
+    z[l] = v;
+    if (logits) logits[static_cast<int64_t>(n) * L + l] = v;
+    mx = fmaxf(mx, v);
+  }
+  mx = block_reduce(mx, red, true);
+  float se = 0.f;
+  for (int l = t; l < L; l += 256) se += __expf(z[l] - mx);
+  se = block_reduce(se, red, false);
+  const int64_t y64 = y[n];
+  const bool ok = y64 >= 0 && y64 < L;  // an out-of-range label never indexes z
+  const int yn = ok ? static_cast<int>(y64) : -1;
+  float cnt = 0.f;  // (<= 8192 classes: exact in fp32)
+  if (ok) {
+    const float zy = z[yn];
+    for (int l = t; l < L; l += 256) cnt += (z[l] > zy || (z[l] == zy && l < yn)) ? 1.f : 0.f;
+  }
+  cnt = block_reduce(cnt, red, false);
+  if (t == 0) {
+    lrow[n] = ok ? __logf(se) + mx - z[yn] : __int_as_float(0x7fc00000);
+    rank[n] = ok ? static_cast<int32_t>(cnt) : L;
+  }
+}
+
+// totals += (sum loss_n, #rank < 1, #rank < 5, Nb): one thread, image order, plain fp64 adds
+__global__ void head_eval_tail_kernel(const float* __restrict__ lrow, const int32_t* __restrict__ rank, int Nb,
+                                      double* __restrict__ totals) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  double ls = totals[0], t1 = totals[1], t5 = totals[2];
+  for (int n = 0; n < Nb; ++n) {
+    ls += static_cast<double>(lrow[n]);
+    t1 += rank[n] < 1 ? 1.0 : 0.0;
+    t5 += rank[n] < 5 ? 1.0 : 0.0;
+  }
+  totals[0] = ls;
+  totals[1] = t1;
+  totals[2] = t5;
+  totals[3] += static_cast<double>(Nb);
+}
+
 // dfeat[i] = bf16(sum_s part2[s][i]) (8 per thread); block 0 also writes the
 // mean loss, summed over the images in a fixed order.
 __global__ __launch_bounds__(256) void head_fin_kernel(const float* __restrict__ part2, int splits, int64_t nel,
@@ -328,6 +382,24 @@ hipError_t head_forward(const void* x, int Nb, int HW, int C, const void* w, con
   hipLaunchKernelGGL(head_ce_kernel, dim3(Nb), dim3(256), L * sizeof(float), s, part1, s1, Nb, L, head_lpad(L),
                      static_cast<const bf16_t*>(b), y, 1.f / static_cast<float>(Nb), lrow, static_cast<bf16_t*>(dl),
                      static_cast<bf16_t*>(dlT));
+  return hipGetLastError();
+}
+
+hipError_t head_eval(const void* x, int Nb, int HW, int C, const void* w, const void* b, int L, const int64_t* y,
+                     void* feat, float* part1, float* loss_row, int32_t* rank_row, float* logits, double* totals,
+                     hipStream_t s) {
+  if (Nb <= 0 || HW <= 0 || C % 8 || L <= 0 || L > 8192) return hipErrorInvalidValue;
+  int s1, s2;
+  head_splits(Nb, C, L, &s1, &s2);
+  hipLaunchKernelGGL(head_pool_kernel, dim3(Nb, (C + 511) / 512), dim3(256), 0, s, static_cast<const bf16_t*>(x), HW,
+                     C, 1.f / static_cast<float>(HW), static_cast<bf16_t*>(feat));
+  HeadGemm g = make_gemm(static_cast<const bf16_t*>(feat), static_cast<const bf16_t*>(w), Nb, L, C, C, C, s1);
+  g.part = part1;
+  HeadGemm none{};
+  hipLaunchKernelGGL((head_gemm_kernel<false, false>), dim3(g.blocks), dim3(256), 0, s, g, none);
+  hipLaunchKernelGGL(head_eval_kernel, dim3(Nb), dim3(256), L * sizeof(float), s, part1, s1, Nb, L,
+                     static_cast<const bf16_t*>(b), y, loss_row, rank_row, logits);
+  if (totals) hipLaunchKernelGGL(head_eval_tail_kernel, dim3(1), dim3(64), 0, s, loss_row, rank_row, Nb, totals);
   return hipGetLastError();
 }
 

@@ -398,6 +398,16 @@ hipError_t dispatch_epi(const GemmParams& p, int epi, hipStream_t s) {
       case EPI_BIAS_RELU: return launch<BM, BN, WM, WN, GATHER, EPI_BIAS_RELU, MINB, STAGES, BPC>(p, s);
     }
   }
+  // inference epilogues (BN folded into the conv): the two-stage configs (igemm_infer_cfg)
+  if constexpr (STAGES == 2 && GATHER != G_DGRAD2) {
+    if constexpr (GATHER != G_CONV3) {
+      if (epi == EPI_BN) return launch<BM, BN, WM, WN, GATHER, EPI_BN, MINB, STAGES, BPC>(p, s);
+    }
+    if (epi == EPI_BN_RELU) return launch<BM, BN, WM, WN, GATHER, EPI_BN_RELU, MINB, STAGES, BPC>(p, s);
+    if constexpr (GATHER == G_DENSE) {
+      if (epi == EPI_BN_RES_RELU) return launch<BM, BN, WM, WN, GATHER, EPI_BN_RES_RELU, MINB, STAGES, BPC>(p, s);
+    }
+  }
   return hipErrorInvalidValue;
 }
 
@@ -455,6 +465,14 @@ int igemm_pick(int M, int N, int K) {
 }  // namespace gemm
 
 namespace gemm {
+// The inference epilogues (EPI_BN*) are instantiated on the two-stage configs
+// 0-3; the three-stage config 4 (a forced one: igemm_pick never chooses it)
+// runs them on its two-stage twin, config 1 (the same 256x128 tile).
+int igemm_infer_cfg(int cfg, int epi, int N) {
+  (void)epi; (void)N;
+  return cfg == 4 ? 1 : cfg;
+}
+
 hipError_t igemm(const GemmParams& p_in, int epi, int gather, int cfg, hipStream_t s) {
   // timing-only: price one operand's traffic (outputs are wrong): 1 drops A's loads, 2 B's
   static const int price = tune_int("igemm_price", 0);

@@ -23,6 +23,21 @@ hipError_t bn_act_backward(const void* dy, const void* y, const uint8_t* mbits, 
                            void* dres, void* dgamma, void* dbeta, float* ws, int64_t M, int C,
                            int dtype, int pdtype, bool relu, bool training, hipStream_t s);
 
+// Inference coefficients of every BN of a network in one launch: row i writes
+// scale = gamma rsqrt(var + eps) | shift = beta - mean scale (fp32) to
+// out[off : off + 2C]; gamma / beta fp32 or bf16 (pt_bf16), null = 1 / 0.
+struct BnInferRow {
+  const void* gamma;
+  const void* beta;
+  const float* mean;
+  const float* var;
+  int32_t C;
+  int32_t pt_bf16;
+  int64_t off;  // in floats (a multiple of 4: 16-byte aligned slices)
+};
+hipError_t bn_infer_coefs(const BnInferRow* rows, int nrows, float eps, float* out, int64_t out_floats,
+                          hipStream_t s);
+
 // Stem BN + ReLU + max-pool(3, 2, 1), bf16 NHWC x [N, H, W, C], C % 8 == 0.
 // y [N, PH, PW, C]; idx uint8 [N, PH, PW, C] = in-window argmax (kh*3 + kw).
 hipError_t bn_pool_forward(const void* x, void* y, uint8_t* idx, const void* gamma, const void* beta,
@@ -423,7 +438,15 @@ hipError_t stem7x7_wgrad_bn(const void* c0, const void* dp, const uint8_t* idx, 
 // partials), lrow [Nb] per-image loss, dl [Nb][Lp] / dlT [L][Nb] bf16 dlogits
 // (mean reduction).  Backward: part2 [s2][Nb][C] fp32, dfeat [Nb][C] bf16,
 // dW [L][C] / db [L] bf16, loss [1] fp32 (mean).  s1 / s2 from head_splits.
+// Evaluation (head_eval): the same pool + fc, then per image loss_row (bit-equal
+// to head_forward's lrow), rank_row = #{l : z[l] > z[y]} + #{l < y : z[l] == z[y]}
+// (the label is in the top k iff rank < k; a label outside [0, L): loss NaN,
+// rank L), optional fp32 logits [Nb][L], and totals [4] fp64 += (loss sum, top-1
+// hits, top-5 hits, images), added in image order by one thread.  Any Nb.
 void head_splits(int Nb, int C, int L, int* s1, int* s2);
+hipError_t head_eval(const void* x, int Nb, int HW, int C, const void* w, const void* b, int L, const int64_t* y,
+                     void* feat, float* part1, float* loss_row, int32_t* rank_row, float* logits, double* totals,
+                     hipStream_t s);
 int head_lpad(int L);  // dl's row pitch: L rounded up to 8
 hipError_t head_forward(const void* x, int Nb, int HW, int C, const void* w, const void* b, int L, const int64_t* y,
                         void* feat, float* part1, float* lrow, void* dl, void* dlT, hipStream_t s);
@@ -474,6 +497,9 @@ hipError_t spin(hipStream_t s, double microseconds);
 
 // conv GEMM main-loop selection (-1 by shape, 0 register-staged, 1 LDS-DMA)
 int gemm_core_mode();
+// main loop (0 register-staged, 1 LDS-DMA) and tile config of this thread's last
+// conv GEMM launch with an inference epilogue (tests: which instantiation ran)
+void gemm_last_launch(int* core, int* cfg);
 void set_gemm_core_mode(int m);
 // force an LDS-DMA tile config (-1 = by shape; csrc/igemm.hip igemm_pick)
 void set_igemm_cfg(int cfg);

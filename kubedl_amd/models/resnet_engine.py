@@ -90,6 +90,50 @@ def _bfr(t: torch.Tensor) -> torch.Tensor:
     return t.to(torch.bfloat16).float()
 
 
+def label_rank(z: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """Rank of each row's label among its logits ``z`` [N, L]: the number of
+    classes that score higher, ties broken towards the lower class index --
+    ``#{l : z[l] > z[y]} + #{l < y : z[l] == z[y]}``.  The label is in the top k
+    iff ``rank < k``.  A label outside [0, L) ranks L (never in any top k).
+    The rule of csrc/head.hip head_eval_kernel."""
+    n, L = z.shape
+    ok = (y >= 0) & (y < L)
+    yc = torch.where(ok, y, torch.zeros_like(y))
+    zy = z.gather(1, yc.view(-1, 1))
+    idx = torch.arange(L, device=z.device).view(1, -1)
+    rank = ((z > zy) | ((z == zy) & (idx < yc.view(-1, 1)))).sum(1)
+    return torch.where(ok, rank, torch.full_like(rank, L)).to(torch.int32)
+
+
+def eval_rows(z: torch.Tensor, y: torch.Tensor):
+    """(loss_row fp32 [N], rank_row int32 [N]) of fp32 logits ``z`` -- NaN loss
+    for a label outside [0, L), as the training head."""
+    n, L = z.shape
+    ok = (y >= 0) & (y < L)
+    yc = torch.where(ok, y, torch.zeros_like(y))
+    loss = torch.logsumexp(z, 1) - z.gather(1, yc.view(-1, 1)).view(-1)
+    loss = torch.where(ok, loss, torch.full_like(loss, float("nan")))
+    return loss, label_rank(z, y)
+
+
+def add_eval_totals(totals: torch.Tensor, loss_row: torch.Tensor, rank_row: torch.Tensor) -> None:
+    """totals fp64 [4] += (loss sum, top-1 hits, top-5 hits, images)."""
+    totals += torch.stack([loss_row.double().sum(), (rank_row < 1).sum().double(), (rank_row < 5).sum().double(),
+                           torch.tensor(float(loss_row.numel()), dtype=torch.float64, device=totals.device)])
+
+
+def torch_head_eval(fmap, w, b, y, totals, logits=None):
+    """Pool -> fc -> per-image loss and label rank in torch ops, with the
+    rounding points of csrc/head.hip (bf16 pooled features, fp32 logits)."""
+    feat = fmap.mean((2, 3), dtype=torch.float32).to(fmap.dtype).float()
+    z = F.linear(feat, w.float(), b.float() if b is not None else None)
+    if logits is not None:
+        logits.copy_(z)
+    loss_row, rank_row = eval_rows(z, y)
+    add_eval_totals(totals, loss_row, rank_row)
+    return loss_row, rank_row
+
+
 class BNState:
     """Per-layer BatchNorm bookkeeping of one step (module + saved statistics)."""
 
@@ -525,6 +569,85 @@ class HipKernels:
                                loss)
         return loss.view(()), ws["dfeat"]
 
+    # -- inference (BN folded into the conv epilogues, csrc/gemm_epi.h EPI_BN*)
+    def infer_coefs(self, sts):
+        """[2C] scale | shift views, one per BNState, of ONE flat buffer that
+        ONE launch fills from the running statistics (csrc/bn_act.hip
+        bn_infer_coefs).  The pointer table is rebuilt only if a tensor moved
+        (the rule of ResNetEngine._refresh_wt).  Never the workspaces' own
+        coefficient slots: the training step's weight gradients re-read those."""
+        mods = [st.mod for st in sts]
+        ptrs = tuple(t.data_ptr() for m in mods for t in (m.weight, m.bias, m.running_mean, m.running_var))
+        tab = getattr(self, "_ic", None)
+        if tab is None or tab[0] != ptrs:
+            eps = {float(m.eps) for m in mods}
+            assert len(eps) == 1, "bn_infer_coefs: one eps for the whole network"
+            table, n = self.ext.bn_infer_table([(m.weight, m.bias, m.running_mean, m.running_var) for m in mods])
+            buf = torch.empty(n, device=self.dev)
+            offs = table[:, 5].tolist()
+            views = [buf[o:o + 2 * st.C] for o, st in zip(offs, sts)]
+            tab = self._ic = (ptrs, table, buf, views, eps.pop())
+        self.ext.bn_infer_coefs(tab[1], tab[2], tab[4])
+        return tab[3]
+
+    def conv_bn(self, x, w, stride, coef, relu, res=None):
+        """bf16([relu](conv(x, w) * scale + shift [+ res])): a 1x1 (w [Cout, Cin])
+        or 3x3 pad-1 (w [Cout, Cin, 3, 3]) conv with the inference BN, the ReLU
+        and the block's identity in the GEMM epilogue -- one launch, one output."""
+        n, cin, h, wd = x.shape
+        cout = w.shape[0]
+        ho, wo = (h - 1) // stride + 1, (wd - 1) // stride + 1
+        y = _nhwc_empty(n, cout, ho, wo, x)
+        if w.dim() == 4:
+            assert res is None
+            self.ext.conv3x3_bn(x, w, y, n, h, wd, cin, cout, stride, coef, relu)
+        else:
+            self.ext.conv1x1_bn(x, w, y, n * ho * wo, cout, cin, ho, wo, h, wd, stride, coef, relu, res)
+        return y
+
+    def stem_infer(self, x, w, st, coef):
+        """Stem conv without statistics, then BN (running statistics) + ReLU +
+        max-pool in one pass; its coefficient scratch is a workspace of this
+        path's own (``coef`` is not needed: bn_pool_fwd derives the same values)."""
+        if not (tuple(w.shape) == (64, 3, 7, 7) and x.shape[1] == 3 and x.dtype == torch.bfloat16
+                and x.is_contiguous(memory_format=torch.channels_last)):
+            raise ValueError(f"HIP engine stem: 3-channel bf16 NHWC input and a [64, 3, 7, 7] conv expected "
+                             f"(got x {tuple(x.shape)} {x.dtype}, w {tuple(w.shape)})")
+        oh, ow = (x.shape[2] - 1) // 2 + 1, (x.shape[3] - 1) // 2 + 1
+        c0 = _nhwc_empty(x.shape[0], 64, oh, ow, x)
+        wk = w if w.is_contiguous(memory_format=torch.channels_last) else stem_weights(w)
+        self.ext.stem7x7_fwd(x, wk, c0, None, None)
+        ws = getattr(self, "_infer_stem_ws", None)
+        if ws is None:
+            ws = self._infer_stem_ws = torch.zeros(self.ext.bn_workspace_floats(st.C), device=self.dev)
+        m = st.mod
+        return self.ext.bn_pool_fwd(c0, m.weight, m.bias, m.running_mean, m.running_var, False, float(m.momentum),
+                                    float(m.eps), ws, False, False)[0]
+
+    def head_eval_ok(self, fmap, w, y) -> bool:
+        return (fmap.dtype == torch.bfloat16 and w.dtype == torch.bfloat16 and w.is_contiguous()
+                and fmap.is_contiguous(memory_format=torch.channels_last) and fmap.shape[1] % 8 == 0
+                and w.shape[0] <= 8192 and y.dtype == torch.int64)
+
+    def head_eval(self, fmap, w, b, y, totals, logits=None):
+        """Pool -> fc -> per-image loss and label rank -> fp64 totals on
+        csrc/head.hip (any batch size); returns (loss_row, rank_row)."""
+        if not self.head_eval_ok(fmap, w, y):
+            return torch_head_eval(fmap, w, b, y, totals, logits)
+        n, c = fmap.shape[:2]
+        L = w.shape[0]
+        key = ("head_eval", n, c, L)
+        ws = self._dw32.get(key)
+        if ws is None:
+            s1, _ = self.ext.head_splits(n, c, L)
+            ws = self._dw32[key] = dict(feat=torch.empty(n, c, dtype=torch.bfloat16, device=fmap.device),
+                                        part1=torch.empty(s1 * n * L, device=fmap.device),
+                                        lrow=torch.empty(n, device=fmap.device),
+                                        rank=torch.empty(n, dtype=torch.int32, device=fmap.device))
+        yc = y if y.is_contiguous() else y.contiguous()
+        self.ext.head_eval(fmap, w, b, yc, ws["feat"], ws["part1"], ws["lrow"], ws["rank"], logits, totals)
+        return ws["lrow"], ws["rank"]
+
     def _stem_ws(self, nb, device, h=224, w=224):
         key = ("stem", nb, h, w)
         ws = self._dw32.get(key)
@@ -628,6 +751,42 @@ class TorchKernels:
         a, _ = self.bn_apply(c0, st, relu=True)
         y, idx = F.max_pool2d(a.float(), 3, 2, 1, return_indices=True)
         return y.to(c0.dtype).contiguous(memory_format=torch.channels_last), idx
+
+    # -- inference: the same rounding points as the HIP epilogues (the conv output
+    # rounded to the storage precision, then fmaf + residual + ReLU rounded once)
+    @staticmethod
+    def infer_coefs(sts):
+        out = []
+        for st in sts:
+            m = st.mod
+            sc = m.weight.float() * torch.rsqrt(m.running_var + m.eps)
+            out.append(torch.cat([sc, m.bias.float() - m.running_mean * sc]))
+        return out
+
+    @staticmethod
+    def conv_bn(x, w, stride, coef, relu, res=None):
+        if w.dim() == 4:
+            y = F.conv2d(x.float(), w.float(), stride=stride, padding=1)
+        else:
+            y = F.conv2d(x.float()[:, :, ::stride, ::stride], w.float()[:, :, None, None])
+        C = w.shape[0]
+        o = y.to(x.dtype).float() * coef[:C].view(1, -1, 1, 1) + coef[C:].view(1, -1, 1, 1)
+        if res is not None:
+            o = o + res.float()
+        if relu:
+            o = F.relu(o)
+        return o.to(x.dtype).contiguous(memory_format=torch.channels_last)
+
+    @staticmethod
+    def stem_infer(x, w, st, coef):
+        c0 = F.conv2d(x, w, stride=2, padding=3)
+        C = st.C
+        a = F.relu(c0.float() * coef[:C].view(1, -1, 1, 1) + coef[C:].view(1, -1, 1, 1)).to(c0.dtype)
+        return F.max_pool2d(a.float(), 3, 2, 1).to(c0.dtype).contiguous(memory_format=torch.channels_last)
+
+    @staticmethod
+    def head_eval(fmap, w, b, y, totals, logits=None):
+        return torch_head_eval(fmap, w, b, y, totals, logits)
 
     def head_mask_reduce(self, dfeat, hw, mask, x, st, xd=None, std_=None):
         n, c, h, w = x.shape
@@ -1097,6 +1256,44 @@ class ResNetEngine:
             cur = out
         self._saved = (x, c0, idx, saved, cur)
         return cur
+
+    # ------------------------------------------------------------------ inference
+    @torch.no_grad()
+    def infer(self, x: torch.Tensor) -> torch.Tensor:
+        """Inference forward: the last block's feature map, every BatchNorm a
+        fixed per-channel scale | shift from the running statistics, folded --
+        with the ReLU and the residual add -- into the producing conv's epilogue:
+        one launch per conv, no statistics, masks or raw conv outputs, nothing
+        kept.  On the current stream; no training state (running statistics,
+        BN workspaces, saved activations, transposed weights, gradients) is
+        written.  The rounding points are those of the bf16 module in ``eval()``:
+        every BNAct output is one bf16 tensor."""
+        K, m = self.K, self.model
+        mods = [m.bn1] + [b_ for blk in self.blocks for b_ in (blk.bn1, blk.bn2, blk.bn3, blk.down_bn)
+                          if b_ is not None]
+        coef = dict(zip(mods, K.infer_coefs([self.bn[b_] for b_ in mods])))
+        cur = K.stem_infer(x, m.conv1.weight, self.bn[m.bn1], coef[m.bn1])
+        for blk in self.blocks:
+            s = blk.conv2.stride[0]
+            a1 = K.conv_bn(cur, blk.conv1.weight.view(blk.conv1.out_channels, -1), 1, coef[blk.bn1], True)
+            a2 = K.conv_bn(a1, blk.conv2.weight, s, coef[blk.bn2], True)
+            ident = cur
+            if blk.down_conv is not None:
+                ident = K.conv_bn(cur, blk.down_conv.weight.view(blk.down_conv.out_channels, -1),
+                                  blk.down_conv.stride[0], coef[blk.down_bn], False)
+            cur = K.conv_bn(a2, blk.conv3.weight.view(blk.conv3.out_channels, -1), 1, coef[blk.bn3], True, res=ident)
+        return cur
+
+    @torch.no_grad()
+    def evaluate(self, x: torch.Tensor, y: torch.Tensor, totals: torch.Tensor, logits: torch.Tensor | None = None):
+        """``infer`` + the evaluation head: adds this batch to ``totals`` (fp64
+        [4] on the device: loss sum, top-1 hits, top-5 hits, images) without a
+        host read; optionally writes the fp32 ``logits`` [N, L].  Returns the
+        per-image (loss_row, rank_row); a label is in the top k iff rank < k
+        (``label_rank``)."""
+        m = self.model
+        fmap = self.infer(x)
+        return self.K.head_eval(fmap, m.fc.weight, m.fc.bias, y, totals, logits)
 
     # ------------------------------------------------------------------ step
     def forward_backward(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:

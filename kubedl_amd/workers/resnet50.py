@@ -11,12 +11,24 @@ Per step (all on the rank's HIP stream):
   weight-gradient kernels, bucketed RCCL all-reduce of bf16 gradient slices
   overlapped with backward) -> one fused SGD-momentum launch (fp32 master,
   writes bf16 weights).
+
+``--eval-batches E`` scores E held-out synthetic batches per rank after the last
+step (and after every ``--eval-every`` steps, ``xdl_ctr.eval_steps``' schedule):
+the engine's inference forward (BatchNorm from the running statistics, folded
+into the conv epilogues) and the evaluation head, totals all-reduced over the
+ranks; the JSON line gains ``eval_loss`` / ``eval_top1`` / ``eval_top5`` /
+``eval_images`` / ``eval_images_per_sec`` and, with ``--eval-every``,
+``eval_history`` (the evaluations inside the loop; the one after the last step is
+the ``eval_*`` fields themselves).  Evaluation time is kept out of ``seconds`` /
+``images_per_sec``.  ``--eval-only`` loads the latest checkpoint of
+``KDL_CKPT_DIR``, evaluates and exits (2 when there is none); it never trains.
 """
 from __future__ import annotations
 
 import argparse
 import json
 import os
+import sys
 import time
 
 _ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -138,6 +150,9 @@ class ResNetTrainer:
         self.x = x
         self.y = torch.randint(0, num_classes, (batch,), generator=g, device=dev)
         self.batch = batch
+        self.image = image
+        self.num_classes = num_classes
+        self.seed = seed
         self.last_loss = None
         self._loss_work = None
         # (world 1: the caller may build the communicator after the first step;
@@ -211,6 +226,62 @@ class ResNetTrainer:
             self._loss_work = None
         return self._loss_sum / self._loss_div if self._loss_div > 1 else self._loss_sum
 
+    # ------------------------------------------------------------ evaluation
+    def eval_batches(self, n: int):
+        """``n`` held-out synthetic batches of the training batch's shape, from a
+        seeded generator of their own: the training random stream is the same
+        with and without evaluation."""
+        dev = self.info.device
+        g = torch.Generator(device=dev).manual_seed(self.seed + 9000 + self.info.rank)
+        out = []
+        for _ in range(max(n, 0)):
+            if dev.type == "cuda":
+                x = torch.randn(self.batch, self.image, self.image, 3, generator=g, device=dev,
+                                dtype=self.dtype).permute(0, 3, 1, 2)
+            else:
+                x = torch.randn(self.batch, 3, self.image, self.image, generator=g).to(self.dtype)
+            out.append((x, torch.randint(0, self.num_classes, (self.batch,), generator=g, device=dev)))
+        return out
+
+    def evaluate(self, batches) -> dict:
+        """Score ``batches`` (an iterable of (x, y)) with the current weights and
+        running statistics: mean cross-entropy, top-1 and top-5 accuracy over
+        every rank's images.  On the trainer's compute stream, ordered after the
+        last step; totals accumulate on the device in fp64 (counts exact) and
+        cross the ranks in one all-reduce.  Training state is not touched."""
+        dev = self.info.device
+        if self.stream is None:
+            totals = self._evaluate(batches)
+        else:
+            caller = torch.cuda.current_stream(dev)
+            self.stream.wait_stream(caller)
+            with torch.cuda.stream(self.stream):
+                totals = self._evaluate(batches)
+            caller.wait_stream(self.stream)
+        if dist.is_initialized() and not self.defer_collectives:
+            dist.all_reduce(totals)
+        loss, top1, top5, n = totals.tolist()
+        n = int(n)
+        return {"eval_loss": loss / n if n else float("nan"), "eval_top1": top1 / n if n else float("nan"),
+                "eval_top5": top5 / n if n else float("nan"), "eval_images": n}
+
+    @torch.no_grad()
+    def _evaluate(self, batches) -> torch.Tensor:
+        totals = torch.zeros(4, dtype=torch.float64, device=self.info.device)
+        if self.engine is not None:
+            for x, y in batches:
+                self.engine.evaluate(x, y, totals)
+            return totals
+        from kubedl_amd.models.resnet_engine import add_eval_totals, eval_rows
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            for x, y in batches:
+                add_eval_totals(totals, *eval_rows(self.model(x).float(), y))
+        finally:
+            self.model.train(was_training)
+        return totals
+
     def check_transport(self) -> None:
         """Raise if a P2P all-reduce of any step so far timed out.  Call after
         a device synchronisation: the kernels report through host-mapped
@@ -257,8 +328,31 @@ def run(args) -> dict:
         done, st = resumed
         tr.load_state_dict(st)
     total = args.warmup + args.steps
+    E = max(args.eval_batches, 0)
+    if args.eval_only:
+        if resumed is None:
+            print(f"resnet50 --eval-only: no checkpoint in KDL_CKPT_DIR={os.environ.get('KDL_CKPT_DIR', '')!r}",
+                  file=sys.stderr, flush=True)
+            kdist.shutdown(info)
+            return {"rank": info.rank, "exit": 2}
+        eval_set = tr.eval_batches(max(E, 1))
+        sync(info)
+        te = time.perf_counter()
+        ev = tr.evaluate(eval_set)
+        sync(info)
+        ev["eval_images_per_sec"] = ev["eval_images"] / max(time.perf_counter() - te, 1e-9)
+        res = {"rank": info.rank, "world_size": info.world_size, "steps": 0, "resumed_from_step": done, **ev}
+        kdist.shutdown(info)
+        return res
+    from kubedl_amd.workers.xdl_ctr import eval_steps
+    mid_evals = eval_steps(total, E, args.eval_every)
+    eval_set = tr.eval_batches(E)
+    history = []
+    eval_s = 0.0  # time of the in-loop evaluations inside the timed region (subtracted below)
+    timing = False
 
     def one(i):
+        nonlocal eval_s
         t = time.perf_counter()
         tr.step()
         if steplog.enabled:
@@ -269,6 +363,16 @@ def run(args) -> dict:
             tr.check_transport()  # never persist weights of a timed-out all-reduce
             ckpt.save(i + 1, tr.state_dict())
             kdist.barrier(info)  # peers wait for the save instead of racing ahead into timeouts
+        if i + 1 in mid_evals:
+            # an evaluation point inside the loop: drained before and after, its
+            # time taken out of the timed region's accounting
+            sync(info)
+            te = time.perf_counter()
+            ev = tr.evaluate(eval_set)
+            history.append({"step": i + 1, "loss": ev["eval_loss"], "top1": ev["eval_top1"], "top5": ev["eval_top5"]})
+            sync(info)
+            if timing:
+                eval_s += time.perf_counter() - te
         common.maybe_inject_fault(info.rank, i)
 
     for i in range(done, args.warmup):
@@ -278,12 +382,21 @@ def run(args) -> dict:
     sync(info)
     t0 = time.perf_counter()
     timed = range(max(done, args.warmup), total)
+    timing = True
     for i in timed:
         one(i)
     sync(info)
     kdist.barrier(info)
     sync(info)
-    dt = time.perf_counter() - t0
+    dt = time.perf_counter() - t0 - eval_s
+    estats = {}
+    if E > 0:  # the evaluation after the last step: after dt is taken
+        te = time.perf_counter()
+        estats = tr.evaluate(eval_set)
+        sync(info)
+        estats["eval_images_per_sec"] = estats["eval_images"] / max(time.perf_counter() - te, 1e-9)
+        if args.eval_every > 0:
+            estats["eval_history"] = history
     tr.check_transport()
     dt = kdist.all_reduce_max(dt, info)
     nsteps = len(timed)
@@ -294,7 +407,7 @@ def run(args) -> dict:
         "steps_per_sec": nsteps / dt if dt > 0 else 0.0,
         "images_per_sec": nsteps * args.batch * info.world_size / dt if dt > 0 else 0.0,
         "loss": loss, "startup_s": t0 - t_start, "resumed_from_step": done if resumed is not None else None,
-        "total_steps": total,
+        "total_steps": total, **estats,
     }
     steplog.close()
     common.report_progress(total, res["steps_per_sec"], final=True, loss=loss)
@@ -312,12 +425,22 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--cpu", action="store_true")
     ap.add_argument("--bn-backend", default="auto", choices=["auto", "hip", "torch"])
     ap.add_argument("--engine", default="auto", choices=["auto", "fused", "autograd"])
+    ap.add_argument("--eval-batches", type=int, default=0,
+                    help="held-out synthetic batches per rank scored at every evaluation point (inference forward, "
+                         "loss + top-1 + top-5); 0: no evaluation")
+    ap.add_argument("--eval-every", type=int, default=0,
+                    help="also evaluate after every this many steps (warm-up included); 0: only after the last step")
+    ap.add_argument("--eval-only", action="store_true",
+                    help="load the latest checkpoint of KDL_CKPT_DIR, evaluate --eval-batches batches (default 1), "
+                         "print the JSON line and exit; exit status 2 when there is no checkpoint")
     return ap
 
 
 def main(argv=None) -> int:
     args = build_parser().parse_args(argv)
     res = run(args)
+    if "exit" in res:
+        return res["exit"]
     if res["rank"] == 0:
         print(json.dumps(res), flush=True)
     return 0
