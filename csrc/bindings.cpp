@@ -966,6 +966,44 @@ void auc_accumulate(const at::Tensor& logit, const at::Tensor& y, at::Tensor his
             "auc_accumulate");
 }
 
+// image input (csrc/augment.hip): one launch per batch on the current stream
+void augment_batch(const at::Tensor& images, const at::Tensor& labels, const at::Tensor& plan, int64_t row0,
+                   int64_t B, int64_t OH, int64_t OW, const std::vector<double>& A, const std::vector<double>& Bc,
+                   at::Tensor x, at::Tensor y) {
+  TORCH_CHECK(images.is_cuda() && images.scalar_type() == at::kByte && images.dim() == 4 && images.size(3) == 3 &&
+                  images.is_contiguous() && images.size(0) >= 1,
+              "augment_batch: images u8 [n, H, W, 3] contiguous");
+  const int64_t n = images.size(0), H = images.size(1), W = images.size(2);
+  TORCH_CHECK(H >= 1 && W >= 1 && H <= 65536 && W <= 65536, "augment_batch: stored H, W in [1, 65536]");
+  TORCH_CHECK(labels.is_cuda() && labels.scalar_type() == at::kLong && labels.dim() == 1 && labels.is_contiguous() &&
+                  labels.numel() == n,
+              "augment_batch: labels int64 [n] contiguous");
+  TORCH_CHECK(plan.is_cuda() && plan.scalar_type() == at::kInt && plan.dim() == 2 && plan.size(1) == 8 &&
+                  plan.is_contiguous(),
+              "augment_batch: plan int32 [rows, 8] contiguous");
+  TORCH_CHECK(B >= 1 && row0 >= 0 && row0 + B <= plan.size(0) && B < (int64_t(1) << 31),
+              "augment_batch: row0 + B <= rows, B >= 1");
+  TORCH_CHECK(OH >= 1 && OW >= 1 && OH <= 512 && OW <= 512, "augment_batch: OH, OW in [1, 512]");
+  TORCH_CHECK(A.size() == 3 && Bc.size() == 3, "augment_batch: A, Bc of 3 floats");
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.dim() == 4 && x.size(0) == B && x.size(1) == 3 &&
+                  x.size(2) == OH && x.size(3) == OW && x.permute({0, 2, 3, 1}).is_contiguous() &&
+                  reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "augment_batch: x bf16 [B, 3, OH, OW] channels_last, 16-byte aligned");
+  TORCH_CHECK(y.is_cuda() && y.scalar_type() == at::kLong && y.dim() == 1 && y.numel() == B && y.is_contiguous(),
+              "augment_batch: y int64 [B] contiguous");
+  TORCH_CHECK(labels.get_device() == images.get_device() && plan.get_device() == images.get_device() &&
+                  x.get_device() == images.get_device() && y.get_device() == images.get_device(),
+              "augment_batch: one device");
+  const float a[3] = {static_cast<float>(A[0]), static_cast<float>(A[1]), static_cast<float>(A[2])};
+  const float b[3] = {static_cast<float>(Bc[0]), static_cast<float>(Bc[1]), static_cast<float>(Bc[2])};
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(images.device());
+  check_hip(kdl::augment_batch(images.data_ptr<uint8_t>(), labels.data_ptr<int64_t>(), n, static_cast<int>(H),
+                               static_cast<int>(W), plan.data_ptr<int>(), row0, static_cast<int>(B),
+                               static_cast<int>(OH), static_cast<int>(OW), a, b, x.data_ptr(), y.data_ptr<int64_t>(),
+                               cur_stream()),
+            "augment_batch");
+}
+
 at::Tensor auc_finalize(const at::Tensor& hist) {
   check_auc_hist(hist, "auc_finalize");
   const c10::hip::HIPGuardMasqueradingAsCUDA guard(hist.device());
@@ -2099,6 +2137,12 @@ PYBIND11_MODULE(_C, m) {
   m.def("auc_accumulate", &auc_accumulate,
         "streaming AUC: add rows (logit f32 [n], y f32 [n]) into hist int64 [2, 65536] / invalid int64 [1]");
   m.def("auc_finalize", &auc_finalize, "streaming AUC: (U2, P, N) int64 [3] of a histogram");
+  m.def("augment_batch", &augment_batch,
+        "image input: rows row0..row0+B-1 of plan int32 [rows, 8] (src, y0, x0, h, w, flip) crop / resample / flip / "
+        "normalise images u8 [n, H, W, 3] into x bf16 [B, 3, OH, OW] channels_last, y = labels[src]; one launch",
+        py::arg("images"), py::arg("labels"), py::arg("plan"), py::arg("row0"), py::arg("B"), py::arg("OH"),
+        py::arg("OW"), py::arg("A"), py::arg("Bc"), py::arg("x"), py::arg("y"));
+  m.def("augment_tile_rows", &kdl::augment_tile_rows, "output rows one augment_batch block produces");
   m.def("auc_rows_per_block", &kdl::auc_rows_per_block, "rows one auc_accumulate block counts in LDS for n rows");
   m.def("segment_reduce_adagrad", &segment_reduce_adagrad,
         "one-owner sync-free push: per-id gradient sums (segment_reduce) applied by Adagrad in the same launch");

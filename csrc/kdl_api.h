@@ -359,6 +359,18 @@ hipError_t auc_accumulate(const float* logit, const float* y, int64_t n, int64_t
 // exact for P, N < 2^31 (U2 < 2^63).  hist 16-byte aligned.
 hipError_t auc_finalize(const int64_t* hist, int64_t* out, hipStream_t s);
 
+// ---- augment.hip (image input: gather + crop + resample + flip + normalise + bf16)
+// images u8 [n_img, H, W, 3], labels int64 [n_img], plan int32 [rows, 8] =
+// (src, y0, x0, h, w, flip, 0, 0); rows row0 .. row0 + B - 1 of the plan make
+// x bf16 [B, OH, OW, 3] (16-byte aligned) and y int64 [B] = labels[src], one launch.
+// x = bf16(fmaf(float(q), A[c], Bc[c])) with q the integer bilinear sample of
+// kubedl_amd/data/augment.py.  A, Bc: host pointers to 3 floats.  1 <= OH, OW <= 512,
+// H, W <= 65536; image offsets are 64-bit.  src and the box are clamped into range.
+int augment_tile_rows(int OH, int OW);  // output rows one block produces
+hipError_t augment_batch(const uint8_t* images, const int64_t* labels, int64_t n_img, int H, int W, const int* plan,
+                         int64_t row0, int B, int OH, int OW, const float* A, const float* Bc, void* x, int64_t* y,
+                         hipStream_t s);
+
 
 // ---- conv1x1.hip (ResNet 1x1 convs as MFMA GEMMs with fused BN prologue/epilogues)
 // epi: 0 plain, 1 BN-forward stats, 2 ReLU-mask-from-x + BN-backward sums,

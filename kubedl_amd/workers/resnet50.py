@@ -22,6 +22,15 @@ ranks; the JSON line gains ``eval_loss`` / ``eval_top1`` / ``eval_top5`` /
 the ``eval_*`` fields themselves).  Evaluation time is kept out of ``seconds`` /
 ``images_per_sec``.  ``--eval-only`` loads the latest checkpoint of
 ``KDL_CKPT_DIR``, evaluates and exits (2 when there is none); it never trains.
+
+``--data DIR`` trains on an image shard set (kubedl_amd/data: uint8 shards, a
+host-side plan, one fused crop / resample / flip / normalise launch per step)
+instead of the one synthetic batch, ``--data-eval DIR`` evaluates on one, and
+``--epochs`` sizes the run in epochs; the JSON line gains ``data_mode`` /
+``epochs_done`` / ``images_seen`` / ``data_wait_ms`` / ``steps_per_epoch`` /
+``eval_dropped``.  A resumed job reads the batches of its own steps: the batch
+of a step is a pure function of (seed, step, rank, world, batch).  Without
+``--data`` nothing changes.
 """
 from __future__ import annotations
 
@@ -59,7 +68,7 @@ class ResNetTrainer:
                  momentum: float = 0.9, weight_decay: float = 5e-5, tiny: bool = False,
                  bn_backend: str = "auto", bucket_cap_mb: float = 12.0, seed: int = 0,
                  conv_benchmark: bool = False, engine: str = "auto", on_streams_ready=None,
-                 before_collectives=None):
+                 before_collectives=None, train_input=None):
         """``engine``: "fused" runs the step through ``models.resnet_engine``
         (fused 1x1-conv GEMMs + staged BN, explicit backward); "autograd" runs
         the module under autograd; "auto" = fused on the GPU when the model's
@@ -76,7 +85,10 @@ class ResNetTrainer:
         bootstrap there, on a helper thread, so it overlaps the weight init,
         the workspaces and the first transposes instead of following them
         (after the stream touch: RCCL's own streams must not claim the
-        hardware queues first, profiles/r03_stream_touch_ab.txt)."""
+        hardware queues first, profiles/r03_stream_touch_ab.txt).
+
+        ``train_input``: a ``kubedl_amd.data.input.ShardInput`` (see ``set_input``);
+        without one the step trains on the constructor's synthetic batch."""
         self.info = info
         dev = info.device
         if engine == "auto":
@@ -160,6 +172,22 @@ class ResNetTrainer:
         self.defer_collectives = False
         self._loss_sum = None
         self._loss_div = 1
+        self.input = None
+        self.steps_done = 0  # steps taken (a resumed job sets it): the input's step index
+        if train_input is not None:
+            self.set_input(train_input)
+
+    def set_input(self, train_input) -> None:
+        """Train on ``train_input.next(self.steps_done)`` instead of the synthetic
+        batch: each step leaves its batch in ``self.x`` / ``self.y``."""
+        if train_input is not None:
+            if train_input.batch != self.batch or (train_input.OH, train_input.OW) != (self.image, self.image):
+                raise ValueError(f"input makes batch {train_input.batch} of {train_input.OH}x{train_input.OW}, "
+                                 f"the trainer takes batch {self.batch} of {self.image}x{self.image}")
+            if self.num_classes < train_input.shards.classes:
+                raise ValueError(f"{train_input.shards.dir}: {train_input.shards.classes} classes, the model has "
+                                 f"{self.num_classes}")
+        self.input = train_input
 
     def touch_streams(self) -> None:
         """One tiny kernel on each stream the step uses (compute, weight-gradient
@@ -190,6 +218,9 @@ class ResNetTrainer:
 
     def _step_body(self) -> torch.Tensor:
         """The step's device work: returns the loss."""
+        if self.input is not None:
+            self.x, self.y = self.input.next(self.steps_done)
+        self.steps_done += 1
         self.space.zero_grad()
         with trace_range("forward_backward"):
             if self.engine is not None:
@@ -316,10 +347,38 @@ def sync(info: kdist.DistInfo) -> None:
 
 def run(args) -> dict:
     t_start = time.time()
+    if args.steps is None:
+        args.steps = 20
     info = kdist.init_from_env("cpu" if args.cpu else None, world1_group=True)
     common.signal_ready({"rank": info.rank})
+    # image shard sets (kubedl_amd/data): opened before the model, whose class
+    # count comes from their metadata
+    train_shards = eval_shards = None
+    if args.data or args.data_eval:
+        from kubedl_amd.data.input import ShardInput
+        from kubedl_amd.data.shards import ImageShards
+        train_shards = ImageShards.open(args.data) if args.data else None
+        eval_shards = ImageShards.open(args.data_eval) if args.data_eval else None
+    kw = {}
+    if train_shards is not None or eval_shards is not None:
+        kw["num_classes"] = max(s.classes for s in (train_shards, eval_shards) if s is not None)
     tr = ResNetTrainer(info, batch=args.batch, image=args.image, tiny=args.tiny,
-                       bn_backend=args.bn_backend, engine=args.engine)
+                       bn_backend=args.bn_backend, engine=args.engine, **kw)
+    E = max(args.eval_batches, 0)
+
+    def shard_input(shards, train, max_batches=0):
+        if tr.num_classes < shards.classes:
+            raise ValueError(f"{shards.dir}: {shards.classes} classes, the model has {tr.num_classes}")
+        return ShardInput(shards, info, args.batch, args.image, seed=args.data_seed, mode=args.data_mode,
+                          train=train, workers=args.data_workers, resident_gb=args.data_resident_gb,
+                          max_batches=max_batches)
+    train_in = shard_input(train_shards, True) if train_shards is not None and not args.eval_only else None
+    eval_in = shard_input(eval_shards, False, E) if eval_shards is not None else None
+    inputs = [i for i in (train_in, eval_in) if i is not None]
+    if train_in is not None:
+        tr.set_input(train_in)
+        if args.epochs is not None:
+            args.steps = max(args.epochs * train_in.steps_per_epoch - args.warmup, 0)
     ckpt = Checkpointer.from_env(info.rank)
     steplog = StepLog(rank=info.rank)
     done = 0  # optimizer steps completed by this job (across restarts)
@@ -327,26 +386,36 @@ def run(args) -> dict:
     if resumed is not None:
         done, st = resumed
         tr.load_state_dict(st)
+        tr.steps_done = done  # the input continues at the step's own batches (data/plan.py)
     total = args.warmup + args.steps
-    E = max(args.eval_batches, 0)
+    dstats = {}
+    if eval_in is not None:
+        dstats["eval_dropped"] = eval_in.dropped
     if args.eval_only:
         if resumed is None:
             print(f"resnet50 --eval-only: no checkpoint in KDL_CKPT_DIR={os.environ.get('KDL_CKPT_DIR', '')!r}",
                   file=sys.stderr, flush=True)
+            for i in inputs:
+                i.close()
             kdist.shutdown(info)
             return {"rank": info.rank, "exit": 2}
-        eval_set = tr.eval_batches(max(E, 1))
+        eval_set = eval_in if eval_in is not None else tr.eval_batches(max(E, 1))
         sync(info)
         te = time.perf_counter()
         ev = tr.evaluate(eval_set)
         sync(info)
         ev["eval_images_per_sec"] = ev["eval_images"] / max(time.perf_counter() - te, 1e-9)
-        res = {"rank": info.rank, "world_size": info.world_size, "steps": 0, "resumed_from_step": done, **ev}
+        if eval_in is not None:
+            dstats["data_mode"] = eval_in.mode
+        res = {"rank": info.rank, "world_size": info.world_size, "steps": 0, "resumed_from_step": done, **ev, **dstats}
+        for i in inputs:
+            i.close()
         kdist.shutdown(info)
         return res
     from kubedl_amd.workers.xdl_ctr import eval_steps
-    mid_evals = eval_steps(total, E, args.eval_every)
-    eval_set = tr.eval_batches(E)
+    do_eval = E > 0 or eval_in is not None  # --data-eval with --eval-batches 0: the whole set
+    mid_evals = eval_steps(total, 1 if do_eval else 0, args.eval_every)
+    eval_set = eval_in if eval_in is not None else tr.eval_batches(E)
     history = []
     eval_s = 0.0  # time of the in-loop evaluations inside the timed region (subtracted below)
     timing = False
@@ -390,7 +459,7 @@ def run(args) -> dict:
     sync(info)
     dt = time.perf_counter() - t0 - eval_s
     estats = {}
-    if E > 0:  # the evaluation after the last step: after dt is taken
+    if do_eval:  # the evaluation after the last step: after dt is taken
         te = time.perf_counter()
         estats = tr.evaluate(eval_set)
         sync(info)
@@ -409,6 +478,16 @@ def run(args) -> dict:
         "loss": loss, "startup_s": t0 - t_start, "resumed_from_step": done if resumed is not None else None,
         "total_steps": total, **estats,
     }
+    if train_in is not None:
+        dstats.update(data_mode=train_in.mode, steps_per_epoch=train_in.steps_per_epoch,
+                      epochs_done=tr.steps_done // train_in.steps_per_epoch,
+                      images_seen=tr.steps_done * args.batch * info.world_size,
+                      data_wait_ms=train_in.data_wait_ms)
+    elif eval_in is not None:
+        dstats["data_mode"] = eval_in.mode
+    res.update(dstats)
+    for i in inputs:
+        i.close()
     steplog.close()
     common.report_progress(total, res["steps_per_sec"], final=True, loss=loss)
     kdist.shutdown(info)
@@ -417,7 +496,7 @@ def run(args) -> dict:
 
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="ResNet-50 DP bf16 trainer (PyTorchJob worker)")
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps after the warm-up (default 20)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--image", type=int, default=224)
@@ -433,11 +512,44 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--eval-only", action="store_true",
                     help="load the latest checkpoint of KDL_CKPT_DIR, evaluate --eval-batches batches (default 1), "
                          "print the JSON line and exit; exit status 2 when there is no checkpoint")
+    ap.add_argument("--data", default=None, metavar="DIR",
+                    help="train on this image shard set (kubedl_amd/data/shards.py) instead of one synthetic batch; "
+                         "the class count comes from its meta.json")
+    ap.add_argument("--data-eval", default=None, metavar="DIR",
+                    help="evaluate on this shard set instead of synthetic batches; --eval-batches N then caps the "
+                         "batches per rank (0: all of them)")
+    ap.add_argument("--epochs", type=int, default=None,
+                    help="with --data: steps = epochs * steps_per_epoch - warmup (floored at 0); not with --steps")
+    ap.add_argument("--data-mode", default="auto", choices=["auto", "resident", "stream"],
+                    help="resident: the rank's partition lives in HBM; stream: staged from the host per batch; "
+                         "auto: resident when it fits --data-resident-gb")
+    ap.add_argument("--data-resident-gb", type=float, default=None,
+                    help="HBM budget of --data-mode auto (default: 25 %% of the smaller of the free memory and the "
+                         "KDL_HBM_LIMIT_GB slice)")
+    ap.add_argument("--data-workers", type=int, default=4, help="gather threads of --data-mode stream")
+    ap.add_argument("--data-seed", type=int, default=0, help="seed of the image order and the crop boxes")
     return ap
 
 
+def parse_args(argv=None):
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    if args.epochs is not None:
+        if args.steps is not None:
+            ap.error("--epochs and --steps are two ways to say how long to train: give one")
+        if not args.data:
+            ap.error("--epochs needs --data")
+        if args.epochs < 0:
+            ap.error("--epochs >= 0")
+    if args.steps is None:
+        args.steps = 20
+    if args.data_workers < 1:
+        ap.error("--data-workers >= 1")
+    return args
+
+
 def main(argv=None) -> int:
-    args = build_parser().parse_args(argv)
+    args = parse_args(argv)
     res = run(args)
     if "exit" in res:
         return res["exit"]
