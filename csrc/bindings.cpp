@@ -571,6 +571,70 @@ void gbdt_heap_nodes(const at::Tensor& packed, const at::Tensor& out) {
             "gbdt_heap_to_nodes");
 }
 
+// counts int64 [n] += the rows of X that reach each node of trees [t0, t1) (csrc/gbdt_shap.hip); nodes and
+// tree_off as for gbdt_predict
+void gbdt_cover(const at::Tensor& X, const at::Tensor& nodes, const at::Tensor& tree_off, int64_t t0, int64_t t1,
+                const at::Tensor& counts) {
+  TORCH_CHECK(X.is_cuda() && X.scalar_type() == at::kFloat && X.dim() == 2 && X.is_contiguous() && X.size(1) >= 1,
+              "gbdt_cover: X must be a contiguous fp32 [N, F] GPU tensor");
+  TORCH_CHECK(nodes.is_cuda() && nodes.scalar_type() == at::kInt && nodes.dim() == 2 && nodes.size(1) == 4 &&
+                  nodes.is_contiguous() && nodes.numel() < (int64_t{1} << 31),
+              "gbdt_cover: nodes must be a contiguous int32 [n, 4] GPU tensor");
+  TORCH_CHECK(tree_off.is_cuda() && tree_off.scalar_type() == at::kInt && tree_off.dim() == 1 &&
+                  tree_off.is_contiguous(),
+              "gbdt_cover: tree_off must be a contiguous int32 [T + 1] GPU tensor");
+  TORCH_CHECK(counts.is_cuda() && counts.scalar_type() == at::kLong && counts.dim() == 1 && counts.is_contiguous() &&
+                  counts.size(0) == nodes.size(0),
+              "gbdt_cover: counts must be a contiguous int64 [n] GPU tensor, one entry per node");
+  TORCH_CHECK(nodes.device() == X.device() && tree_off.device() == X.device() && counts.device() == X.device(),
+              "gbdt_cover: tensors on different devices");
+  TORCH_CHECK(0 <= t0 && t0 <= t1 && t1 < tree_off.numel(), "gbdt_cover: tree range [", t0, ", ", t1,
+              ") outside the ", tree_off.numel() - 1, " trees of tree_off");
+  TORCH_CHECK(X.size(1) <= (1 << 20), "gbdt_cover: at most 2^20 features");
+  if (X.size(0) == 0 || t0 == t1) return;
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(X.device());
+  check_hip(kdl::gbdt_cover(X.data_ptr<float>(), X.size(0), static_cast<int>(X.size(1)),
+                            reinterpret_cast<const kdl::GbdtNode*>(nodes.data_ptr<int32_t>()),
+                            static_cast<int>(nodes.size(0)), tree_off.data_ptr<int32_t>(), static_cast<int>(t0),
+                            static_cast<int>(t1), counts.data_ptr<int64_t>(), cur_stream()),
+            "gbdt_cover");
+}
+
+// out [N, K, F + 1] = the path table's feature contributions of X's rows, bias[k] in the last column
+// (csrc/gbdt_shap.hip).  paths int32 [slots, 4]; chunk_off int32 [chunks + 1]; class_chunk int32 [K + 1]
+void gbdt_contribs(const at::Tensor& X, const at::Tensor& paths, const at::Tensor& chunk_off,
+                   const at::Tensor& class_chunk, const at::Tensor& bias, int64_t K, const at::Tensor& out) {
+  TORCH_CHECK(X.is_cuda() && X.scalar_type() == at::kFloat && X.dim() == 2 && X.is_contiguous() && X.size(1) >= 1,
+              "gbdt_contribs: X must be a contiguous fp32 [N, F] GPU tensor");
+  TORCH_CHECK(X.size(1) < (1 << 20), "gbdt_contribs: fewer than 2^20 features");
+  TORCH_CHECK(1 <= K && K <= 32, "gbdt_contribs: 1 <= K <= 32");
+  TORCH_CHECK(paths.is_cuda() && paths.scalar_type() == at::kInt && paths.dim() == 2 && paths.size(1) == 4 &&
+                  paths.is_contiguous() && paths.numel() < (int64_t{1} << 31),
+              "gbdt_contribs: paths must be a contiguous int32 [slots, 4] GPU tensor");
+  TORCH_CHECK(chunk_off.is_cuda() && chunk_off.scalar_type() == at::kInt && chunk_off.dim() == 1 &&
+                  chunk_off.is_contiguous() && chunk_off.numel() >= 1,
+              "gbdt_contribs: chunk_off must be a contiguous int32 [chunks + 1] GPU tensor");
+  TORCH_CHECK(class_chunk.is_cuda() && class_chunk.scalar_type() == at::kInt && class_chunk.dim() == 1 &&
+                  class_chunk.is_contiguous() && class_chunk.numel() == K + 1,
+              "gbdt_contribs: class_chunk must be a contiguous int32 [K + 1] GPU tensor");
+  TORCH_CHECK(bias.is_cuda() && bias.scalar_type() == at::kFloat && bias.dim() == 1 && bias.is_contiguous() &&
+                  bias.numel() == K,
+              "gbdt_contribs: bias must be a contiguous fp32 [K] GPU tensor");
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kFloat && out.dim() == 3 && out.is_contiguous() &&
+                  out.size(0) == X.size(0) && out.size(1) == K && out.size(2) == X.size(1) + 1,
+              "gbdt_contribs: out must be a contiguous fp32 [N, K, F + 1] GPU tensor");
+  TORCH_CHECK(paths.device() == X.device() && chunk_off.device() == X.device() &&
+                  class_chunk.device() == X.device() && bias.device() == X.device() && out.device() == X.device(),
+              "gbdt_contribs: tensors on different devices");
+  if (X.size(0) == 0) return;
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(X.device());
+  check_hip(kdl::gbdt_contribs(X.data_ptr<float>(), X.size(0), static_cast<int>(X.size(1)), paths.data_ptr<int32_t>(),
+                               static_cast<int>(paths.size(0)), chunk_off.data_ptr<int32_t>(),
+                               static_cast<int>(chunk_off.numel() - 1), class_chunk.data_ptr<int32_t>(),
+                               bias.data_ptr<float>(), static_cast<int>(K), out.data_ptr<float>(), cur_stream()),
+            "gbdt_contribs");
+}
+
 // ------------------------------------------------------------------ CTR
 at::Tensor gemm_bias_act(const at::Tensor& a, const at::Tensor& w, const c10::optional<at::Tensor>& bias, bool relu,
                          bool trans_w) {
@@ -2096,6 +2160,11 @@ PYBIND11_MODULE(_C, m) {
   m.def("gbdt_route", &gbdt_route, "GBDT row routing (1 = right child)");
   m.def("gbdt_predict", &gbdt_predict, "forest inference: margin[n, t % K] += tree t's leaf value for t in [t0, t1)");
   m.def("gbdt_heap_nodes", &gbdt_heap_nodes, "the grower's [4, heap] arrays -> packed forest nodes, on the device");
+  m.def("gbdt_cover", &gbdt_cover, "cover pass: counts[node] += rows of X reaching the node, trees [t0, t1)");
+  m.def("gbdt_contribs", &gbdt_contribs, "exact TreeSHAP of a path table: out[N, K, F + 1]");
+  m.def("gbdt_contribs_chunk_slots", &kdl::gbdt_contribs_chunk_slots, "16-byte path slots per LDS chunk (whole paths)");
+  m.def("gbdt_contribs_rows_per_block", &kdl::gbdt_contribs_rows_per_block,
+        "rows per block of the contribution kernel for F features (0: nothing staged in LDS)");
   m.def("gbdt_predict_chunk_nodes", &kdl::gbdt_predict_chunk_nodes, "forest nodes per LDS chunk (whole trees)");
   m.def("gbdt_predict_rows_per_block", &kdl::gbdt_predict_rows_per_block,
         "rows per block for (F, K): 256 / 128 / 64, 0 = rows not staged in LDS");

@@ -255,6 +255,20 @@ int gbdt_predict_rows_per_block(int F, int K);   // 256 / 128 / 64, or 0: rows n
 // the grower's [4, heap] fp32 (feature, split bin, threshold, value) -> heap GbdtNodes (left = 2i + 1)
 hipError_t gbdt_heap_to_nodes(const float* packed, int heap, GbdtNode* out, hipStream_t s);
 
+// ---- gbdt_shap.hip (feature contributions: HistGBDT.set_background / predict_contribs)
+// counts[node] += rows of X that reach the node, for the nodes of trees [t0, t1) (predict's routing and
+// node table; integer atomics, so order independent).  counts: int64 [num_nodes]
+hipError_t gbdt_cover(const float* X, int64_t N, int F, const GbdtNode* nodes, int num_nodes, const int32_t* tree_off,
+                      int t0, int t1, int64_t* counts, hipStream_t s);
+// out [N, K, F + 1] = exact path-dependent TreeSHAP of the path table (layout: gbdt_shap.hip's header;
+// paths int32 [num_slots, 4], chunk_off int32 [num_chunks + 1], class_chunk int32 [K + 1]); the last
+// column is bias[k].  Every element is written; one lane owns a row, no atomics; 1 <= K <= 32
+hipError_t gbdt_contribs(const float* X, int64_t N, int F, const int32_t* paths, int num_slots,
+                         const int32_t* chunk_off, int num_chunks, const int32_t* class_chunk, const float* bias,
+                         int K, float* out, hipStream_t s);
+int gbdt_contribs_chunk_slots();          // 16-byte path slots per LDS chunk (whole paths)
+int gbdt_contribs_rows_per_block(int F);  // 256 / 128 / 64, or 0: rows and accumulators not in LDS
+
 // ---- ctr.hip (XDLJob CTR model: MFMA GEMM, embeddings, sparse Adagrad)
 // b_kn: B is [K][N] (C = A B), else [N][K] (C = A B^T)
 hipError_t gemm_bias_act(const void* A, const void* B, const void* bias, bool bias_bf16, void* C, int M, int N, int K,

@@ -36,6 +36,12 @@ staged in LDS, leaves added in tree order -- bit-identical to
 same kernel over a tree range advances the validation margin of
 ``fit(eval_set=...)`` straight from the grower's heap arrays (early stopping,
 ``evals_result``).  ``save`` / ``load`` keep a model as JSON.
+
+Feature contributions: ``set_background`` counts the background rows that reach
+each node (the covers) and ``predict_contribs`` returns exact path-dependent
+TreeSHAP values [N, K, F + 1] (csrc/gbdt_shap.hip: the cover kernel and the
+contribution kernel over a host-built table of root-to-leaf paths; on CPU the
+same path formula on torch ops in fp64).
 """
 from __future__ import annotations
 
@@ -132,6 +138,8 @@ class HistGBDT:
         self.best_iteration: Optional[int] = None
         self.best_score: Optional[float] = None
         self._forest_cache = None  # (key, trees kept alive, nodes, tree_off, max feature): _forest()
+        self._cover_cache = None  # (forest key, int64 covers [num_nodes], background F): set_background()
+        self._paths_cache = None  # (key, path table): _path_table()
 
     # ------------------------------------------------------------ quantisation
     def fit_cuts(self, X: torch.Tensor, sample: int = 65536, seed: int = 0) -> None:
@@ -723,6 +731,232 @@ class HistGBDT:
         if self.p.objective == "binary:logistic":
             return torch.sigmoid(margin[:, 0])
         return margin[:, 0]
+
+    # ------------------------------------------------------------ feature contributions
+    def set_background(self, X: torch.Tensor) -> torch.Tensor:
+        """The covers ``predict_contribs`` weighs unknown features with: per node of
+        the packed forest, the number of rows of ``X`` (this rank's shard; summed over
+        the ranks of a process group) that reach it under ``predict``'s routing.
+        int64 [num_nodes], kept beside the forest cache (not saved with the model) and
+        dropped when ``trees`` is replaced.  On the GPU this is the cover kernel of
+        csrc/gbdt_shap.hip, on CPU a torch traversal."""
+        if X.dim() != 2:
+            raise ValueError(f"set_background: X must be [N, F], got {tuple(X.shape)}")
+        if self.cuts is not None and X.shape[1] != self.cuts.shape[0]:
+            raise ValueError(f"set_background: X has {X.shape[1]} features, the model was fitted on "
+                             f"{self.cuts.shape[0]}")
+        X = X.to(self.device).float().contiguous()
+        rows = _allreduce_(torch.tensor([X.shape[0]], dtype=torch.int64, device=self.device))
+        if int(rows) == 0:
+            raise ValueError("set_background: an empty background set")
+        nodes, off, max_feat = self._forest()
+        if max_feat >= X.shape[1]:
+            raise ValueError(f"set_background: the trees split on feature {max_feat}, X has {X.shape[1]} features")
+        counts = torch.zeros(nodes.shape[0], dtype=torch.int64, device=self.device)
+        if self.use_hip and X.is_cuda:
+            _ext.load().gbdt_cover(X, nodes, off, 0, off.numel() - 1, counts)
+        else:
+            self._cover_torch(X, nodes, off, counts)
+        _allreduce_(counts)
+        self._cover_cache = (self._forest_cache[0], counts, X.shape[1])
+        self._paths_cache = None
+        return counts
+
+    @staticmethod
+    def _cover_torch(X: torch.Tensor, nodes: torch.Tensor, off: torch.Tensor, counts: torch.Tensor) -> None:
+        """counts[node] += rows of X reaching the node, on torch ops (the CPU path and
+        the reference of csrc/gbdt_shap.hip's cover kernel)."""
+        offs = off.tolist()
+        for o, e in zip(offs, offs[1:]):
+            if e == o:
+                continue
+            feat, left = nodes[o:e, 0].long(), nodes[o:e, 2].long()
+            thr = nodes[o:e, 1].contiguous().view(torch.float32)
+            rows = torch.arange(X.shape[0], device=X.device)
+            node = torch.zeros_like(rows)
+            while rows.numel():
+                counts[o:e] += torch.bincount(node, minlength=e - o)
+                f = feat[node]
+                m = f >= 0
+                rows, node, f = rows[m], node[m], f[m]
+                node = left[node] + (~(X[rows, f] <= thr[node])).long()
+
+    def _path_table(self, n_rounds: int) -> dict:
+        """The first ``n_rounds`` rounds as root-to-leaf paths (csrc/gbdt_shap.hip's
+        header has the layout): per path the leaf value and one merged element per
+        distinct feature -- ``lo`` (largest right-turn threshold, NaN: none), ``hi``
+        (smallest left-turn threshold, with a has-left flag) and the zero fraction
+        ``z`` = prod cover[child] / cover[parent] over the feature's splits (0 / 0 := 0),
+        in fp64 until the end.  Class-major, cut into chunks of whole paths.  Cached per
+        (forest, covers, n_rounds)."""
+        import numpy as np
+        nodes, off, _ = self._forest()
+        c = self._cover_cache
+        if c is None or c[0] != self._forest_cache[0]:
+            raise ValueError("predict_contribs: no background set for these trees (call set_background(X) first)")
+        key = (c[0], id(c[1]), n_rounds)
+        if self._paths_cache is not None and self._paths_cache[0] == key:
+            return self._paths_cache[1]
+        K = self._num_class()
+        nd, offs, cover = nodes.cpu().numpy(), off.cpu().tolist(), c[1].cpu().tolist()
+        nan = math.nan
+        p_v, p_m, p_cls = [], [], []                                  # per path
+        e_path, e_j, e_f, e_lo, e_hi, e_hl, e_z = [], [], [], [], [], [], []  # per element
+        bias = [0.0] * K
+        for k in range(K):
+            for t in range(k, n_rounds * K, K):
+                o, e = offs[t], offs[t + 1]
+                feat, left = nd[o:e, 0].tolist(), nd[o:e, 2].tolist()
+                thr = np.ascontiguousarray(nd[o:e, 1]).view(np.float32).tolist()
+                val = np.ascontiguousarray(nd[o:e, 3]).view(np.float32).tolist()
+                stack = [(0, ())] if e > o else []
+                while stack:
+                    i, elems = stack.pop()
+                    f = feat[i]
+                    if f < 0:
+                        z_all = 1.0
+                        for j, (ef, lo, hi, hl, z) in enumerate(elems):
+                            e_path.append(len(p_v)); e_j.append(j); e_f.append(ef); e_lo.append(lo)
+                            e_hi.append(hi); e_hl.append(hl); e_z.append(z)
+                            z_all *= z
+                        bias[k] += val[i] * z_all
+                        if elems:
+                            p_v.append(val[i]); p_m.append(len(elems)); p_cls.append(k)
+                        continue
+                    th, cp = thr[i], cover[o + i]
+                    at = next((j for j, el in enumerate(elems) if el[0] == f), -1)
+                    for child, is_left in ((left[i] + 1, False), (left[i], True)):  # the left child is popped first
+                        frac = cover[o + child] / cp if cp > 0 else 0.0
+                        _, lo, hi, hl, z = elems[at] if at >= 0 else (f, nan, 0.0, False, 1.0)
+                        if is_left:  # x <= hi and x <= th; a NaN threshold lets nothing through
+                            hi = th if not hl else hi if hi != hi else th if th != th else min(hi, th)
+                            hl = True
+                        elif th == th:  # !(x <= lo) and !(x <= th); a NaN threshold lets everything through
+                            lo = th if lo != lo else max(lo, th)
+                        el = (f, lo, hi, hl, z * frac)
+                        new = elems[:at] + (el,) + elems[at + 1:] if at >= 0 else elems + (el,)
+                        if len(new) > 10:
+                            raise ValueError("predict_contribs: a root-to-leaf path splits on more than 10 features")
+                        stack.append((child, new))
+        m = np.asarray(p_m, dtype=np.int64)
+        length = 1 + m + (m + 3) // 4
+        start = np.concatenate([[0], np.cumsum(length)]).astype(np.int64)
+        if start[-1] >= 2 ** 29:
+            raise ValueError("predict_contribs: path table of 2^29 or more slots")
+        # chunks of whole paths, none across a class boundary
+        limit = _ext.load().gbdt_contribs_chunk_slots() if self.use_hip else 512
+        chunk_off, class_chunk, cur = [0], [0] * (K + 1), 0
+        for p in range(len(m)):
+            if p_cls[p] != cur or start[p + 1] - chunk_off[-1] > limit:
+                if start[p] > chunk_off[-1]:
+                    chunk_off.append(int(start[p]))
+                for kk in range(cur + 1, p_cls[p] + 1):
+                    class_chunk[kk] = len(chunk_off) - 1
+                cur = p_cls[p]
+        if start[-1] > chunk_off[-1]:
+            chunk_off.append(int(start[-1]))
+        for kk in range(cur + 1, K + 1):
+            class_chunk[kk] = len(chunk_off) - 1
+        ep, ej = np.asarray(e_path, dtype=np.int64), np.asarray(e_j, dtype=np.int64)
+        ef, ehl = np.asarray(e_f, dtype=np.int64), np.asarray(e_hl, dtype=bool)
+        elo, ehi, ez = (np.asarray(a, dtype=np.float64) for a in (e_lo, e_hi, e_z))
+        slots = np.zeros((int(start[-1]), 4), dtype=np.int32)
+        fl = slots.view(np.float32)
+        head = start[:-1]
+        fl[head, 0] = np.asarray(p_v, dtype=np.float32)
+        slots[head, 1] = m
+        at = head[ep] + 1 + ej
+        slots[at, 0] = ef | (ehl.astype(np.int64) << 30)
+        fl[at, 1], fl[at, 2], fl[at, 3] = elo, ehi, ez
+        fl[head[ep] + 1 + m[ep] + ej // 4, ej % 4] = 1.0 - ez  # rounded from fp64, not formed in fp32
+        # the same paths padded to [P, M] for the torch path
+        M = int(m.max()) if len(m) else 0
+        pad = {"feat": np.zeros((len(m), M), dtype=np.int64), "lo": np.full((len(m), M), nan),
+               "hi": np.zeros((len(m), M)), "hl": np.zeros((len(m), M), dtype=bool), "z": np.ones((len(m), M)),
+               "valid": np.zeros((len(m), M), dtype=bool)}
+        for name, a in (("feat", ef), ("lo", elo), ("hi", ehi), ("hl", ehl), ("z", ez), ("valid", True)):
+            pad[name][ep, ej] = a
+        pad["v"], pad["cls"] = np.asarray(p_v, dtype=np.float64), np.asarray(p_cls, dtype=np.int64)
+        base = float(self._base(1)[0, 0])
+        dev = self.device
+        table = {"slots": torch.from_numpy(slots).to(dev),
+                 "chunk_off": torch.tensor(chunk_off, dtype=torch.int32, device=dev),
+                 "class_chunk": torch.tensor(class_chunk, dtype=torch.int32, device=dev),
+                 "bias64": [b + base for b in bias], "pad": pad}
+        table["bias"] = torch.tensor(table["bias64"], dtype=torch.float32, device=dev)
+        self._paths_cache = (key, table)
+        return table
+
+    def _contribs_torch(self, X: torch.Tensor, table: dict) -> torch.Tensor:
+        """``predict_contribs`` on torch ops, fp64 inside: the kernel's path formula
+        (Gauss-Legendre in t, prefix and suffix products) over padded paths, a block of
+        rows and paths at a time.  The CPU path."""
+        import numpy as np
+        N, F = X.shape
+        K = self._num_class()
+        dev = X.device
+        pad = {k: torch.from_numpy(v).to(dev) for k, v in table["pad"].items()}
+        P, M = pad["feat"].shape
+        phi = torch.zeros(N, K * (F + 1), dtype=torch.float64, device=dev)
+        if P and N:
+            Q = (M + 1) // 2  # exact for degree M - 1
+            gx, gw = np.polynomial.legendre.leggauss(Q)
+            tq = torch.from_numpy((gx + 1) / 2).to(dev)
+            wq = torch.from_numpy(gw / 2).to(dev)
+            nr = min(N, 65536)
+            pc = max(1, (1 << 22) // (nr * M * Q))
+            for r0 in range(0, N, nr):
+                Xr = X[r0:r0 + nr].double()
+                n = Xr.shape[0]
+                one = torch.ones(n, 1, 1, Q, dtype=torch.float64, device=dev)
+                for p0 in range(0, P, pc):
+                    s = slice(p0, p0 + pc)
+                    f, z, valid = pad["feat"][s], pad["z"][s], pad["valid"][s]
+                    xv = Xr[:, f.reshape(-1)].view(n, -1, M)
+                    o = (~(xv <= pad["lo"][s]) & (~pad["hl"][s] | (xv <= pad["hi"][s]))) | ~valid
+                    fac = o.double()[..., None] * tq + (z[..., None] * (1 - tq))
+                    fac = torch.where(valid[..., None], fac, torch.ones_like(fac))
+                    ones = one.expand(n, fac.shape[1], 1, Q)
+                    pre = torch.cat([ones, fac[:, :, :-1]], 2).cumprod(2)
+                    suf = torch.cat([fac[:, :, 1:], ones], 2).flip(2).cumprod(2).flip(2)
+                    W = (pre * suf * wq).sum(-1)
+                    d = torch.where(o, 1.0 - z, -z) * valid
+                    term = pad["v"][s][:, None] * d * W
+                    idx = (pad["cls"][s][:, None] * (F + 1) + f).reshape(-1)
+                    phi[r0:r0 + n].index_add_(1, idx, term.reshape(n, -1))
+        phi = phi.view(N, K, F + 1)
+        phi[:, :, F] = torch.tensor(table["bias64"], dtype=torch.float64, device=dev)
+        return phi.float()
+
+    def predict_contribs(self, X: torch.Tensor, n_rounds: Optional[int] = None) -> torch.Tensor:
+        """Per-feature contributions to the raw margin, fp32 [N, K, F + 1]: exact
+        path-dependent TreeSHAP with the covers of ``set_background`` (row counts), the
+        Shapley values of ``S -> sum over the class's trees of E_t(x, S)``.  Column ``F``
+        is the bias (the expected margin over the background plus the base margin); the
+        last axis sums to ``predict(X, output_margin=True)`` up to rounding.
+        ``n_rounds`` as in ``predict``.  On the GPU this is the contribution kernel of
+        csrc/gbdt_shap.hip, on CPU the same formula on torch ops in fp64."""
+        if X.dim() != 2:
+            raise ValueError(f"predict_contribs: X must be [N, F], got {tuple(X.shape)}")
+        if self.cuts is not None and X.shape[1] != self.cuts.shape[0]:
+            raise ValueError(f"predict_contribs: X has {X.shape[1]} features, the model was fitted on "
+                             f"{self.cuts.shape[0]}")
+        total = len(self.trees)
+        if n_rounds is None:
+            n_rounds = total if self.best_iteration is None else self.best_iteration + 1
+        if not 0 <= n_rounds <= total:
+            raise ValueError(f"predict_contribs: n_rounds {n_rounds} outside the model's {total} rounds")
+        table = self._path_table(n_rounds)
+        if X.shape[1] != self._cover_cache[2]:
+            raise ValueError(f"predict_contribs: X has {X.shape[1]} features, the background set had "
+                             f"{self._cover_cache[2]}")
+        X = X.to(self.device).float().contiguous()
+        if self.use_hip and X.is_cuda:
+            out = torch.empty(X.shape[0], self._num_class(), X.shape[1] + 1, dtype=torch.float32, device=self.device)
+            _ext.load().gbdt_contribs(X, table["slots"], table["chunk_off"], table["class_chunk"], table["bias"],
+                                      out.shape[1], out)
+            return out
+        return self._contribs_torch(X, table)
 
     # ------------------------------------------------------------ model file
     FORMAT_VERSION = 1

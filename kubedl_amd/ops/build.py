@@ -47,6 +47,11 @@ def _common_flags(abi: int):
     ]
 
 
+# extra flags per HIP source.  gbdt_shap.hip: plain fp32 ops only (no packed v_pk_*_f32 pairs), so
+# that every product and sum rounds once, as the error bound of tests/test_gbdt_contribs.py counts them
+FILE_FLAGS = {"gbdt_shap.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+
+
 def _headers_digest() -> str:
     h = hashlib.sha256()
     for p in sorted(CSRC.glob("*.h")):
@@ -88,8 +93,8 @@ def build(force: bool = False, jobs: int | None = None, verbose: bool = True, ou
     srcs = sorted(CSRC.glob("*.hip")) + sorted(CSRC.glob("*.cpp"))
     jobs = jobs or min(8, os.cpu_count() or 4)
     with cf.ThreadPoolExecutor(jobs) as ex:
-        futs = {ex.submit(_compile, s, hip_flags if s.suffix == ".hip" else cpp_flags, hdr, force, bdir): s
-                for s in srcs}
+        futs = {ex.submit(_compile, s, (hip_flags if s.suffix == ".hip" else cpp_flags) + FILE_FLAGS.get(s.name, []),
+                          hdr, force, bdir): s for s in srcs}
         objs = []
         for f in cf.as_completed(futs):
             objs.append(f.result())

@@ -28,7 +28,12 @@ anything else lives in the pod sandbox) on every rank, predicts the rank's row
 shard, writes the predictions to ``<model file>.pred.rank<R>.npy`` and rank 0
 prints one JSON line with the metric against the labels and the prediction
 rate (the second of two ``predict`` calls, synchronised on both sides; the
-first pays for code loading and forest packing).  A missing model file is an
+first pays for code loading and forest packing).  With ``--pred_contribs`` it
+also writes the per-feature contributions [rows, K, F + 1] of
+``HistGBDT.predict_contribs`` to ``<model file>.contribs.rank<R>.npy`` (the
+background set is every rank's shard, the covers all-reduced) and adds
+``contribs_seconds`` and the largest ``|sum of contributions - margin|`` to the
+JSON line.  A missing model file is an
 error (exit code 2), never a retrain.  ``examples/xgboost/`` has a Train and a
 Predict job spec that share a model path.
 """
@@ -112,12 +117,28 @@ def run_predict(args, info) -> int:
     np.save(out_path, pred.cpu().numpy())
     common.report_progress(1, final=True)
     met = model.metric(margin, y.to(info.device))
+    extra = {}
+    if args.pred_contribs:
+        # the background is every rank's shard: set_background all-reduces the covers
+        model.set_background(X)
+        model.predict_contribs(X)  # code loading + path table
+        sync()
+        t0 = time.perf_counter()
+        phi = model.predict_contribs(X)
+        sync()
+        cdt = kdist.all_reduce_max(time.perf_counter() - t0, info)
+        gap = float((phi.double().sum(-1) - margin.double()).abs().max()) if X.shape[0] else 0.0
+        contribs_path = f"{path}.contribs.rank{info.rank}.npy"
+        np.save(contribs_path, phi.cpu().numpy())
+        extra = {"contribs_seconds": cdt, "contribs_max_abs_sum_minus_margin": kdist.all_reduce_max(gap, info),
+                 "contribs": contribs_path}
     if info.rank == 0:
         print(json.dumps({"job_type": "Predict", "rank": info.rank, "world_size": info.world_size,
                           "objective": model.p.objective, "rounds": len(model.trees), "rows": int(X.shape[0]),
                           "features": int(X.shape[1]), "predict_seconds": dt,
                           "predict_rows_per_sec": X.shape[0] / dt if dt > 0 else 0.0, "model": path,
-                          "predictions": out_path, "device": str(info.device), "hip_kernels": model.use_hip, **met}),
+                          "predictions": out_path, "device": str(info.device), "hip_kernels": model.use_hip, **met,
+                          **extra}),
               flush=True)
     return 0
 
@@ -140,6 +161,7 @@ def main(argv=None) -> int:
     ap.add_argument("--cpu", action="store_true")
     ap.add_argument("--eval_fraction", type=float, default=0.0)
     ap.add_argument("--early_stopping_rounds", type=int, default=0)
+    ap.add_argument("--pred_contribs", action="store_true")
     args, _unknown = ap.parse_known_args(argv)
     if os.environ.get("KDL_RANK"):
         os.environ["RANK"] = os.environ["KDL_RANK"]
