@@ -635,6 +635,75 @@ void gbdt_contribs(const at::Tensor& X, const at::Tensor& paths, const at::Tenso
             "gbdt_contribs");
 }
 
+// g, h fp32 [N, 1] of rank:pairwise / rank:ndcg (csrc/gbdt_rank.hip).  plan_wave / plan_block int32 [*, 4]: the
+// host-built work plan; dtab fp32 [L]: the discount table, L >= max_group; disc fp32 [N]: workspace
+std::vector<at::Tensor> gbdt_rank_grad_hess(const at::Tensor& score, const at::Tensor& label,
+                                            const at::Tensor& plan_wave, const at::Tensor& plan_block,
+                                            const at::Tensor& dtab, int64_t max_group, const at::Tensor& disc,
+                                            bool ndcg) {
+  TORCH_CHECK(score.is_cuda() && score.scalar_type() == at::kFloat && score.dim() == 1 && score.is_contiguous() &&
+                  score.numel() < (int64_t{1} << 31),
+              "gbdt_rank_grad_hess: score must be a contiguous fp32 [N] GPU tensor, N < 2^31");
+  const int64_t N = score.numel();
+  TORCH_CHECK(label.is_cuda() && label.scalar_type() == at::kInt && label.dim() == 1 && label.is_contiguous() &&
+                  label.numel() == N,
+              "gbdt_rank_grad_hess: label must be a contiguous int32 [N] GPU tensor");
+  for (const at::Tensor* p : {&plan_wave, &plan_block})
+    TORCH_CHECK(p->is_cuda() && p->scalar_type() == at::kInt && p->dim() == 2 && p->size(1) == 4 &&
+                    p->is_contiguous() && p->size(0) < (int64_t{1} << 31),
+                "gbdt_rank_grad_hess: a plan must be a contiguous int32 [records, 4] GPU tensor");
+  TORCH_CHECK(dtab.is_cuda() && dtab.scalar_type() == at::kFloat && dtab.dim() == 1 && dtab.is_contiguous() &&
+                  dtab.numel() >= 1 && dtab.numel() < (int64_t{1} << 31) && dtab.numel() >= max_group,
+              "gbdt_rank_grad_hess: dtab must be a contiguous fp32 GPU tensor no shorter than the longest group");
+  TORCH_CHECK(disc.is_cuda() && disc.scalar_type() == at::kFloat && disc.dim() == 1 && disc.is_contiguous() &&
+                  disc.numel() == N,
+              "gbdt_rank_grad_hess: disc must be a contiguous fp32 [N] GPU tensor");
+  TORCH_CHECK(label.device() == score.device() && plan_wave.device() == score.device() &&
+                  plan_block.device() == score.device() && dtab.device() == score.device() &&
+                  disc.device() == score.device(),
+              "gbdt_rank_grad_hess: tensors on different devices");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(score.device());
+  auto g = at::empty({N, 1}, score.options()), h = at::empty({N, 1}, score.options());
+  if (N == 0) return {g, h};
+  check_hip(kdl::gbdt_rank_grad_hess(score.data_ptr<float>(), label.data_ptr<int32_t>(), N,
+                                     plan_wave.data_ptr<int32_t>(), static_cast<int>(plan_wave.size(0)),
+                                     plan_block.data_ptr<int32_t>(), static_cast<int>(plan_block.size(0)),
+                                     dtab.data_ptr<float>(), static_cast<int>(dtab.numel()), disc.data_ptr<float>(),
+                                     ndcg, g.data_ptr<float>(), h.data_ptr<float>(), cur_stream()),
+            "gbdt_rank_grad_hess");
+  return {g, h};
+}
+
+// dcg fp64 [Q]: per group the sum over its rows with pos < k (k <= 0: all) of (2^label - 1) * dtab[pos]
+at::Tensor gbdt_rank_ndcg(const at::Tensor& score, const at::Tensor& label, const at::Tensor& group_ptr,
+                          const at::Tensor& dtab, int64_t max_group, int64_t k) {
+  TORCH_CHECK(score.is_cuda() && score.scalar_type() == at::kFloat && score.dim() == 1 && score.is_contiguous() &&
+                  score.numel() < (int64_t{1} << 31),
+              "gbdt_rank_ndcg: score must be a contiguous fp32 [N] GPU tensor, N < 2^31");
+  TORCH_CHECK(label.is_cuda() && label.scalar_type() == at::kInt && label.dim() == 1 && label.is_contiguous() &&
+                  label.numel() == score.numel(),
+              "gbdt_rank_ndcg: label must be a contiguous int32 [N] GPU tensor");
+  TORCH_CHECK(group_ptr.is_cuda() && group_ptr.scalar_type() == at::kInt && group_ptr.dim() == 1 &&
+                  group_ptr.is_contiguous() && group_ptr.numel() >= 1,
+              "gbdt_rank_ndcg: group_ptr must be a contiguous int32 [Q + 1] GPU tensor");
+  TORCH_CHECK(dtab.is_cuda() && dtab.scalar_type() == at::kFloat && dtab.dim() == 1 && dtab.is_contiguous() &&
+                  dtab.numel() >= 1 && dtab.numel() < (int64_t{1} << 31) && dtab.numel() >= max_group,
+              "gbdt_rank_ndcg: dtab must be a contiguous fp32 GPU tensor no shorter than the longest group");
+  TORCH_CHECK(label.device() == score.device() && group_ptr.device() == score.device() &&
+                  dtab.device() == score.device(),
+              "gbdt_rank_ndcg: tensors on different devices");
+  TORCH_CHECK(k < (int64_t{1} << 31), "gbdt_rank_ndcg: k < 2^31");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(score.device());
+  const int64_t Q = group_ptr.numel() - 1;
+  auto dcg = at::empty({Q}, score.options().dtype(at::kDouble));
+  check_hip(kdl::gbdt_rank_ndcg(score.data_ptr<float>(), label.data_ptr<int32_t>(), score.numel(),
+                                group_ptr.data_ptr<int32_t>(), static_cast<int>(Q), dtab.data_ptr<float>(),
+                                static_cast<int>(dtab.numel()), static_cast<int>(k < 0 ? 0 : k),
+                                dcg.data_ptr<double>(), cur_stream()),
+            "gbdt_rank_ndcg");
+  return dcg;
+}
+
 // ------------------------------------------------------------------ CTR
 at::Tensor gemm_bias_act(const at::Tensor& a, const at::Tensor& w, const c10::optional<at::Tensor>& bias, bool relu,
                          bool trans_w) {
@@ -2162,7 +2231,12 @@ PYBIND11_MODULE(_C, m) {
   m.def("gbdt_heap_nodes", &gbdt_heap_nodes, "the grower's [4, heap] arrays -> packed forest nodes, on the device");
   m.def("gbdt_cover", &gbdt_cover, "cover pass: counts[node] += rows of X reaching the node, trees [t0, t1)");
   m.def("gbdt_contribs", &gbdt_contribs, "exact TreeSHAP of a path table: out[N, K, F + 1]");
-  m.def("gbdt_contribs_chunk_slots", &kdl::gbdt_contribs_chunk_slots, "16-byte path slots per LDS chunk (whole paths)");
+  m.def("gbdt_rank_grad_hess", &gbdt_rank_grad_hess, "rank:pairwise / rank:ndcg g, h [N, 1] over a host-built plan");
+  m.def("gbdt_rank_ndcg", &gbdt_rank_ndcg, "per group DCG@k in fp64 [Q] (k <= 0: the whole list)");
+  m.def("gbdt_rank_wave_max", &kdl::gbdt_rank_wave_max, "largest group of the one-wave path");
+  m.def("gbdt_rank_tile_rows", &kdl::gbdt_rank_tile_rows, "rows per (group, i-tile) block item");
+  m.def("gbdt_rank_chunk_rows", &kdl::gbdt_rank_chunk_rows, "j rows per LDS chunk");
+  m.def("gbdt_contribs_chunk_slots",&kdl::gbdt_contribs_chunk_slots, "16-byte path slots per LDS chunk (whole paths)");
   m.def("gbdt_contribs_rows_per_block", &kdl::gbdt_contribs_rows_per_block,
         "rows per block of the contribution kernel for F features (0: nothing staged in LDS)");
   m.def("gbdt_predict_chunk_nodes", &kdl::gbdt_predict_chunk_nodes, "forest nodes per LDS chunk (whole trees)");

@@ -269,6 +269,22 @@ hipError_t gbdt_contribs(const float* X, int64_t N, int F, const int32_t* paths,
 int gbdt_contribs_chunk_slots();          // 16-byte path slots per LDS chunk (whole paths)
 int gbdt_contribs_rows_per_block(int F);  // 256 / 128 / 64, or 0: rows and accumulators not in LDS
 
+// ---- gbdt_rank.hip (learning to rank: the LambdaMART pair kernels and the DCG of ndcg@k)
+// g, h [N] of rank:pairwise (ndcg = false) or rank:ndcg over a host-built plan (layout: gbdt_rank.hip's header):
+// plan_wave int32 [wave_slots, 4] (groups of <= gbdt_rank_wave_max() rows), plan_block int32 [block_items, 4]
+// (tiles of gbdt_rank_tile_rows() rows of larger groups).  dtab fp32 [dlen]: the discount table, dlen >= the
+// longest group; disc fp32 [N]: workspace, disc[row] = dtab[pos(row)] on return (ndcg only).  A row of no plan
+// record is not written.  No atomics: bit-reproducible
+hipError_t gbdt_rank_grad_hess(const float* score, const int32_t* label, int64_t N, const int32_t* plan_wave,
+                               int wave_slots, const int32_t* plan_block, int block_items, const float* dtab, int dlen,
+                               float* disc, bool ndcg, float* g, float* h, hipStream_t s);
+// dcg[q] = sum over the rows of group q with pos < k (k <= 0: all) of (2^label - 1) * dtab[pos], in fp64
+hipError_t gbdt_rank_ndcg(const float* score, const int32_t* label, int64_t N, const int32_t* group_ptr, int Q,
+                          const float* dtab, int dlen, int k, double* dcg, hipStream_t s);
+int gbdt_rank_wave_max();    // the largest group of the wave path (64)
+int gbdt_rank_tile_rows();   // rows per block item (256)
+int gbdt_rank_chunk_rows();  // j rows per LDS chunk (1024)
+
 // ---- ctr.hip (XDLJob CTR model: MFMA GEMM, embeddings, sparse Adagrad)
 // b_kn: B is [K][N] (C = A B), else [N][K] (C = A B^T)
 hipError_t gemm_bias_act(const void* A, const void* B, const void* bias, bool bias_bf16, void* C, int M, int N, int K,

@@ -42,6 +42,36 @@ each node (the covers) and ``predict_contribs`` returns exact path-dependent
 TreeSHAP values [N, K, F + 1] (csrc/gbdt_shap.hip: the cover kernel and the
 contribution kernel over a host-built table of root-to-leaf paths; on CPU the
 same path formula on torch ops in fp64).
+
+Learning to rank: objectives ``rank:pairwise`` and ``rank:ndcg`` (LambdaMART).  On the
+GPU the gradient is the pair kernels of csrc/gbdt_rank.hip over a work plan built
+once per ``fit``; on CPU the same definition on torch ops in fp64, rounded once.  The
+definition, shared by both paths and by the tests:
+
+* Groups: ``fit(X, y, group=sizes)``, ``sizes`` int [Q], positive, summing to N; the
+  rows of a group are contiguous and in the given order (XGBoost's ``set_group``).
+  ``group_ptr`` (int32 [Q + 1]) lives on the device.  A group lives on one rank:
+  nothing new is all-reduced in training.
+* Labels: integer relevance in [0, 31]; gain ``G(y) = 2^y - 1``.
+* Position: ``pos_i`` is the 0-based position of row i in its group sorted by score,
+  descending, ties to the lower row index (at round 0 every score ties).
+* Discount: ``D[p]`` is the fp64 value ``1 / log2(p + 2)`` rounded once to fp32, a
+  host-built table as long as the longest group, uploaded once per fit.  Every path
+  indexes that fp32 table; no ``log`` runs on the device.
+* ``inv_idcg[q]``: the group's ideal DCG (``sum_p G(y sorted descending)[p] * D[p]`` in
+  fp64), inverted and rounded to fp32; 0 where the ideal DCG is 0.  Once per fit.
+* Pair terms: for every ordered pair ``i != j`` of one group with ``y_i != y_j``, ``hi``
+  the row of the larger label and ``lo`` the other, ``d = s_hi - s_lo``,
+  ``rho = 1 / (1 + exp(d))``, ``w = 1`` (``rank:pairwise``) or
+  ``|G(y_i) - G(y_j)| * |D[pos_i] - D[pos_j]| * inv_idcg[q]`` (``rank:ndcg``):
+  ``g_i += (i is hi ? -1 : +1) * rho * w``, ``h_i += rho * (1 - rho) * w``; at the end
+  ``h_i = max(h_i, 1e-16)``.  No pair sampling, truncation or score normalisation: a
+  pure function of (scores, labels, groups).
+* Base margin 0, one tree per round, ``transform_margin`` is the identity.
+* Metric: ``ndcg@k`` = the mean over groups of ``DCG@k / IDCG@k`` (``DCG@k = sum over
+  pos_i < k of G(y_i) * D[pos_i]`` in fp64; a group whose ``IDCG@k`` is 0 counts as
+  1), ``k = GBDTParams.eval_at``, 0 = the whole list; the metric is named ``ndcg`` for
+  ``k = 0`` and ``ndcg@k`` otherwise.  Higher is better: early stopping maximises it.
 """
 from __future__ import annotations
 
@@ -57,6 +87,9 @@ import torch.distributed as dist
 
 from kubedl_amd.ops import _ext
 
+RANK_OBJECTIVES = ("rank:pairwise", "rank:ndcg")
+MAX_RANK_LABEL = 31
+
 
 @dataclass
 class GBDTParams:
@@ -71,6 +104,7 @@ class GBDTParams:
     min_child_weight: float = 1.0
     base_score: float = 0.5
     early_stopping_rounds: int = 0  # 0 = off (fit's ``early_stopping_rounds`` argument overrides it)
+    eval_at: int = 0  # ranking objectives: the k of ndcg@k, 0 = the whole list
 
     @classmethod
     def parse(cls, spec: str, **kw) -> "GBDTParams":
@@ -205,8 +239,19 @@ class HistGBDT:
         return out
 
     # ------------------------------------------------------------ objectives
-    def _grad_hess(self, pred: torch.Tensor, y: torch.Tensor):
+    def _grad_hess(self, pred: torch.Tensor, y: torch.Tensor, rank: Optional[dict] = None):
         obj = self.p.objective
+        if obj in RANK_OBJECTIVES:
+            if rank is None:
+                raise ValueError(f"{obj} needs the query groups: fit(X, y, group=sizes)")
+            if self.use_hip and pred.is_cuda:
+                # csrc/gbdt_rank.hip: the pair kernels over the fit's plan
+                g, h = _ext.load().gbdt_rank_grad_hess(pred.view(-1), rank["y"], rank["plan_wave"], rank["plan_block"],
+                                                       rank["dtab"], rank["max_group"], rank["disc"],
+                                                       obj == "rank:ndcg")
+                return g, h
+            g, h, _ = self._rank_grad_hess_torch(pred.view(-1), rank)
+            return g.view(-1, 1), h.view(-1, 1)
         if self.use_hip and pred.is_cuda:
             # csrc/gbdt.hip grad_hess_kernel: one launch, the torch composition's expressions
             code = 0 if obj.startswith("reg:") else 1 if obj == "binary:logistic" else 2 if obj.startswith("multi:") else -1
@@ -231,11 +276,155 @@ class HistGBDT:
         K = self.p.num_class if self.p.objective.startswith("multi:") else 1
         if self.p.objective == "binary:logistic":
             b = math.log(self.p.base_score / (1 - self.p.base_score))
-        elif self.p.objective.startswith("multi:"):
+        elif self.p.objective.startswith("multi:") or self.p.objective in RANK_OBJECTIVES:
             b = 0.0
         else:
             b = self.p.base_score
         return torch.full((n, K), b, dtype=torch.float32, device=self.device)
+
+    # ------------------------------------------------------------ learning to rank
+    def _ndcg_name(self) -> str:
+        k = int(self.p.eval_at)
+        return f"ndcg@{k}" if k > 0 else "ndcg"
+
+    def _rank_setup(self, y: torch.Tensor, group, plan: bool = True) -> dict:
+        """Check the groups and labels and build, once per fit (eval set, ``metric`` call),
+        what the ranking paths share: ``group_ptr``, the int32 labels, the discount table,
+        ``inv_idcg`` and ``IDCG@k`` (module docstring) and, with ``plan`` on the GPU, the
+        work plan of csrc/gbdt_rank.hip (its header has the layout) and the ``disc``
+        workspace."""
+        import numpy as np
+        dev = self.device
+        sizes = torch.as_tensor(group).detach().cpu().reshape(-1)
+        if sizes.dtype.is_floating_point or sizes.dtype == torch.bool:
+            raise ValueError("group: integer sizes expected")
+        sizes = sizes.numpy().astype(np.int64)
+        n, Q = int(y.shape[0]), int(sizes.size)
+        if Q and int(sizes.min()) <= 0:
+            raise ValueError(f"group: sizes must be positive (smallest: {int(sizes.min())})")
+        if int(sizes.sum()) != n:
+            raise ValueError(f"group: the sizes sum to {int(sizes.sum())}, there are {n} rows")
+        if n >= 2 ** 31:
+            raise ValueError("ranking: 2^31 or more rows on one rank")
+        yl = y.reshape(-1)
+        if yl.shape[0] != n:
+            raise ValueError(f"ranking: y must hold one label per row, got {tuple(y.shape)}")
+        if n and (yl.dtype.is_floating_point and bool((yl != yl.round()).any())
+                  or int(yl.min()) < 0 or int(yl.max()) > MAX_RANK_LABEL):
+            raise ValueError(f"ranking: labels must be integers in [0, {MAX_RANK_LABEL}]")
+        y32 = yl.to(device=dev, dtype=torch.int32).contiguous()
+        ptr = np.zeros(Q + 1, dtype=np.int64)
+        ptr[1:] = np.cumsum(sizes)
+        L = max(int(sizes.max()) if Q else 1, 1)
+        dtab = (1.0 / np.log2(np.arange(L, dtype=np.float64) + 2.0)).astype(np.float32)
+        gid = torch.repeat_interleave(torch.arange(Q, device=dev), torch.from_numpy(sizes).to(dev))
+        # the ideal order: labels descending inside each group (one device sort); the sums on the host, fp64, in order
+        ys = (MAX_RANK_LABEL - torch.sort(gid * 32 + (MAX_RANK_LABEL - y32.long())).values % 32).cpu().numpy()
+        pos = np.arange(n, dtype=np.int64) - np.repeat(ptr[:-1], sizes)
+        term = (np.ldexp(1.0, ys.astype(np.int32)) - 1.0) * dtab.astype(np.float64)[pos]
+        k = int(self.p.eval_at)
+        idcg = np.add.reduceat(term, ptr[:-1]) if Q else np.zeros(0)
+        idcg_k = np.add.reduceat(np.where(pos < k, term, 0.0), ptr[:-1]) if (Q and k > 0) else idcg
+        with np.errstate(divide="ignore"):
+            inv = np.where(idcg > 0, 1.0 / idcg, 0.0).astype(np.float32)
+        rk = {"Q": Q, "n": n, "sizes": sizes, "ptr_host": ptr, "y": y32, "gid": gid, "max_group": L,
+              "ptr": torch.from_numpy(ptr.astype(np.int32)).to(dev), "dtab": torch.from_numpy(dtab).to(dev),
+              "inv_idcg": torch.from_numpy(inv).to(dev), "idcg_k": torch.from_numpy(idcg_k).to(dev)}
+        if plan and self.use_hip:
+            ext = _ext.load()
+            wmax, tile = ext.gbdt_rank_wave_max(), ext.gbdt_rank_tile_rows()
+            bits = inv.view(np.int32).astype(np.int64)
+
+            def by_size(sel):  # largest first: the waves of a block get groups of similar length
+                idx = np.flatnonzero(sel)
+                return idx[np.argsort(-sizes[idx], kind="stable")]
+            small, big = by_size(sizes <= wmax), by_size(sizes > wmax)
+            tiles = (sizes[big] + tile - 1) // tile
+            rep = np.repeat(big, tiles)
+            i0 = (np.arange(int(tiles.sum()), dtype=np.int64) - np.repeat(np.cumsum(tiles) - tiles, tiles)) * tile
+            wave = np.stack([ptr[small], sizes[small], bits[small], small], 1).astype(np.int32)
+            block = np.stack([ptr[rep], sizes[rep], bits[rep], i0], 1).astype(np.int32)
+            rk["plan_wave"] = torch.from_numpy(wave).to(dev)
+            rk["plan_block"] = torch.from_numpy(block).to(dev)
+            rk["disc"] = torch.zeros(n, dtype=torch.float32, device=dev)
+        return rk
+
+    @staticmethod
+    def _rank_positions_torch(score: torch.Tensor, rk: dict) -> torch.Tensor:
+        """pos [N] (int64): two stable sorts, by score descending and then by group."""
+        o1 = torch.sort(-score, stable=True).indices
+        order = o1[torch.sort(rk["gid"][o1], stable=True).indices]  # rows by (group, score descending, index)
+        pos = torch.empty_like(order)
+        pos[order] = torch.arange(order.numel(), device=score.device) - rk["ptr"].long()[rk["gid"]]
+        return pos
+
+    def _rank_grad_hess_torch(self, score: torch.Tensor, rk: dict):
+        """The ranking gradient on torch ops (the CPU path): fp64 inside, rounded once.
+        Groups of similar size are padded to [c, L] and their pairs formed as [c, i, L]
+        blocks of at most 2^22 elements.  Returns g, h, disc (fp32 [N])."""
+        ndcg = self.p.objective == "rank:ndcg"
+        dev, n = score.device, rk["n"]
+        s, y = score.double(), rk["y"].long()
+        G = torch.ldexp(torch.ones(n, dtype=torch.float64, device=dev), rk["y"]) - 1.0
+        disc = rk["dtab"].double()[self._rank_positions_torch(score, rk)] if ndcg else torch.zeros_like(s)
+        inv = rk["inv_idcg"].double()
+        g, h = torch.zeros_like(s), torch.zeros_like(s)
+        if "chunks" not in rk:  # (groups, padded length), by size
+            import numpy as np
+            sizes = rk["sizes"]
+            order = np.argsort(sizes, kind="stable")
+            chunks, a = [], 0
+            while a < len(order):
+                L = int(sizes[order[a]])
+                b = a + 1
+                while b < len(order) and (b + 1 - a) * int(sizes[order[b]]) ** 2 <= 1 << 22:
+                    L = int(sizes[order[b]])
+                    b += 1
+                chunks.append((torch.from_numpy(order[a:b]).to(dev), L))
+                a = b
+            rk["chunks"] = chunks
+        ptr, nq_all = rk["ptr"].long(), torch.from_numpy(rk["sizes"]).to(dev)
+        for qs, L in rk["chunks"]:
+            ar = torch.arange(L, device=dev)
+            valid = ar[None, :] < nq_all[qs][:, None]                                    # [c, L]
+            idx = torch.where(valid, ptr[qs][:, None] + ar[None, :], torch.zeros_like(ar)[None, :])
+            S, Y, Gc, Dc = s[idx], y[idx], G[idx], disc[idx]
+            gc, hc = torch.zeros_like(S), torch.zeros_like(S)
+            step = max(1, (1 << 22) // (L * len(qs)))
+            for a in range(0, L, step):
+                i = slice(a, a + step)
+                hi = Y[:, i, None] > Y[:, None, :]
+                d = torch.where(hi, S[:, i, None] - S[:, None, :], S[:, None, :] - S[:, i, None])
+                e = torch.exp(-d.abs())
+                r = 1.0 / (1.0 + e)
+                sm = e * r  # the smaller of rho and 1 - rho, never formed by subtraction
+                rho = torch.where(d > 0, sm, r)
+                w = ((Y[:, i, None] != Y[:, None, :]) & valid[:, i, None] & valid[:, None, :]).double()
+                if ndcg:
+                    w = w * (Gc[:, i, None] - Gc[:, None, :]).abs() * (Dc[:, i, None] - Dc[:, None, :]).abs() \
+                        * inv[qs][:, None, None]
+                gc[:, i] = (torch.where(hi, -rho, rho) * w).sum(2)
+                hc[:, i] = (sm * r * w).sum(2)
+            g[idx[valid]], h[idx[valid]] = gc[valid], hc[valid]
+        return g.float(), h.float().clamp_min_(1e-16), disc.float()
+
+    def _ndcg_sum(self, score: torch.Tensor, rk: dict) -> torch.Tensor:
+        """The sum over this rank's groups of ``DCG@k / IDCG@k`` (1 where IDCG@k is 0), one
+        fp64 scalar on the device; the DCG is csrc/gbdt_rank.hip's on the GPU."""
+        k, Q = int(self.p.eval_at), rk["Q"]
+        if Q == 0:
+            return torch.zeros((), dtype=torch.float64, device=self.device)
+        if self.use_hip and score.is_cuda:
+            dcg = _ext.load().gbdt_rank_ndcg(score, rk["y"], rk["ptr"], rk["dtab"], rk["max_group"], k)
+        else:
+            pos = self._rank_positions_torch(score, rk)
+            term = (torch.ldexp(torch.ones(rk["n"], dtype=torch.float64, device=score.device), rk["y"]) - 1.0) \
+                * rk["dtab"].double()[pos]
+            if k > 0:
+                term = torch.where(pos < k, term, torch.zeros_like(term))
+            dcg = torch.zeros(Q, dtype=torch.float64, device=score.device).index_add_(0, rk["gid"], term)
+        idcg = rk["idcg_k"]
+        return torch.where(idcg > 0, dcg / idcg.clamp_min(1e-300), torch.ones_like(dcg)).sum()
 
     # ------------------------------------------------------------ kernels (HIP or torch)
     def _hist(self, bins, g, h, rows, seg_cpu, F, B):
@@ -420,7 +609,7 @@ class HistGBDT:
         return time.perf_counter()
 
     def fit(self, X: torch.Tensor, y: torch.Tensor, log_every: int = 0, callback=None, eval_set=None,
-            early_stopping_rounds: Optional[int] = None):
+            early_stopping_rounds: Optional[int] = None, group=None):
         """``stats['setup_s']``: host->device copy, cut fitting, quantisation and the
         grower's workspaces; ``stats['boost_s']``: the boosting rounds alone (one
         synchronisation at each end, none inside).
@@ -432,7 +621,18 @@ class HistGBDT:
         on the device until the end of ``fit`` (one copy); with it one value is read
         per round, training stops once the metric has not improved for that many
         rounds (every rank at the same round), ``best_iteration`` / ``best_score``
-        are set, all grown trees are kept and ``predict`` defaults to the best round."""
+        are set, all grown trees are kept and ``predict`` defaults to the best round.
+
+        ``group=sizes`` (the ranking objectives only, and required there): the query
+        group sizes of this rank's rows, see the module docstring; ``eval_set`` is then
+        ``(Xv, yv, groupv)`` and the metric ``ndcg@k``, which early stopping maximises."""
+        ranking = self.p.objective in RANK_OBJECTIVES
+        if ranking and group is None:
+            raise ValueError(f"{self.p.objective} needs the query groups: fit(X, y, group=sizes)")
+        if not ranking and group is not None:
+            raise ValueError(f"group is for the ranking objectives, not {self.p.objective}")
+        if ranking and X.shape[0] != y.shape[0]:
+            raise ValueError(f"fit: {X.shape[0]} rows of X for {y.shape[0]} labels")
         t0 = self._sync_time()
         host_cuts = {}
         th = None
@@ -468,6 +668,7 @@ class HistGBDT:
         K = pred.shape[1]
         tc = self._sync_time()
         grower = self._device_grower(bins)
+        rank = self._rank_setup(y, group) if ranking else None
         t1 = self._sync_time()
         for k, v in (("setup_h2d_s", ta - t0), ("setup_cuts_s", tb - ta), ("setup_quantise_s", tc - tb),
                      ("setup_grower_s", t1 - tc)):
@@ -475,7 +676,7 @@ class HistGBDT:
         dev_trees = []
         ev = self._eval_begin(eval_set, early_stopping_rounds, grower) if eval_set is not None else None
         for it in range(self.p.n_estimators):
-            g_all, h_all = self._grad_hess(pred, y)
+            g_all, h_all = self._grad_hess(pred, y, rank)
             round_trees = []
             for k in range(K):
                 g = g_all[:, k].contiguous()
@@ -536,7 +737,10 @@ class HistGBDT:
         return row.sum(dtype=torch.float64)
 
     def _eval_begin(self, eval_set, early_stopping_rounds, grower) -> dict:
-        Xv, yv = eval_set
+        ranking = self.p.objective in RANK_OBJECTIVES
+        if ranking and len(eval_set) != 3:
+            raise ValueError(f"{self.p.objective}: eval_set must be (Xv, yv, groupv)")
+        Xv, yv = eval_set[:2] if ranking else eval_set
         Xv = Xv.to(self.device).float().contiguous()
         yv = yv.to(self.device)
         if Xv.dim() != 2 or Xv.shape[1] != self.cuts.shape[0] or yv.shape[0] != Xv.shape[0]:
@@ -548,10 +752,16 @@ class HistGBDT:
         self.eval_metric = "mlogloss" if obj.startswith("multi:") else "logloss" if obj == "binary:logistic" else "rmse"
         self.evals_result = []
         self.best_iteration = self.best_score = None
+        count = float(Xv.shape[0])
+        rank = None
+        if ranking:  # ndcg@k: a mean over groups, and the one metric here where higher is better
+            self.eval_metric = self._ndcg_name()
+            rank = self._rank_setup(yv, eval_set[2], plan=False)
+            count = float(rank["Q"])
         ev = {"X": Xv, "y": yv, "margin": self._base(Xv.shape[0]), "sums": [], "esr": int(esr or 0),
-              "best": math.inf, "best_it": 0,
-              # the validation rows of every rank, reduced once
-              "count": _allreduce_(torch.tensor([float(Xv.shape[0])], dtype=torch.float64, device=self.device))}
+              "best": -math.inf if ranking else math.inf, "best_it": 0, "rank": rank,
+              # the validation rows (ranking: groups) of every rank, reduced once
+              "count": _allreduce_(torch.tensor([count], dtype=torch.float64, device=self.device))}
         if ev["esr"] > 0:
             ev["count_host"] = float(ev["count"])  # read once, before the rounds
         if grower is not None:
@@ -577,12 +787,15 @@ class HistGBDT:
                 ext.gbdt_predict(ev["X"], ev["nodes"], ev["off"], 0, len(round_trees), ev["margin"])
         else:
             self._add_trees_torch(ev["X"], ev["margin"], [round_trees])
-        s = _allreduce_(self._loss_sum(ev["margin"], ev["y"]).view(1))
+        if ev["rank"] is not None:
+            s = _allreduce_(self._ndcg_sum(ev["margin"].view(-1), ev["rank"]).view(1))
+        else:
+            s = _allreduce_(self._loss_sum(ev["margin"], ev["y"]).view(1))
         ev["sums"].append(s)
         if ev["esr"] <= 0:
             return False
         v = self._eval_value(float(s), ev["count_host"])  # the one small read of the round
-        if v < ev["best"]:
+        if (v > ev["best"]) if ev["rank"] is not None else (v < ev["best"]):
             ev["best"], ev["best_it"] = v, it
             return False
         return it - ev["best_it"] >= ev["esr"]
@@ -1009,8 +1222,16 @@ class HistGBDT:
             m.trees.append(trees)
         return m
 
-    def metric(self, pred: torch.Tensor, y: torch.Tensor) -> dict:
+    def metric(self, pred: torch.Tensor, y: torch.Tensor, group=None) -> dict:
         obj = self.p.objective
+        if obj in RANK_OBJECTIVES:
+            if group is None:
+                raise ValueError(f"{obj}: the metric needs the query groups: metric(pred, y, group=sizes)")
+            if pred.shape[0] != y.shape[0]:
+                raise ValueError(f"metric: {pred.shape[0]} predictions for {y.shape[0]} labels")
+            rk = self._rank_setup(y.to(self.device), group, plan=False)
+            score = pred.to(self.device).reshape(pred.shape[0], -1)[:, 0].float().contiguous()
+            return {self._ndcg_name(): float(self._ndcg_sum(score, rk)) / rk["Q"] if rk["Q"] else 1.0}
         if obj.startswith("multi:"):
             pr = torch.softmax(pred, 1)
             ll = -torch.log(pr.gather(1, y.long()[:, None]).clamp_min(1e-15)).mean()

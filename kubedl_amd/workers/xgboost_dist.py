@@ -12,7 +12,12 @@ the process-group rank comes from ``KDL_RANK`` when present.
 
 Data: ``--dataset iris`` (scikit-learn's bundled copy; every rank takes a
 row shard) or ``--dataset synthetic`` (``--rows`` x ``--features`` float
-rows per rank with a nonlinear target, HIGGS-like shape).
+rows per rank with a nonlinear target, HIGGS-like shape).  With
+``--objective_hint rank`` the synthetic rows come in query groups of about
+``--group_size`` rows (``load_groups``: fixed seed, whole groups on every rank), the
+label is a 0-4 relevance grade, the default objective ``rank:ndcg``, and Train and
+Predict both report ``ndcg@k`` (``eval_at:k`` in ``--xgboost_parameter``; ``ndcg`` for
+the whole list); ``--eval_fraction`` then holds out whole groups.
 
 ``--job_type=Train`` (the default) fits a model, prints one JSON line with the
 training metric and rounds/s, and rank 0 writes the model to ``--model_path``
@@ -69,9 +74,29 @@ def load_data(args, rank: int, world: int):
     logit = X[:, 0] * 1.5 - X[:, 1] ** 2 + X[:, 2] * X[:, 3] + 0.5 * torch.sin(3 * X[:, 4 % args.features])
     if args.objective_hint == "binary":
         y = (logit + 0.3 * torch.randn(args.rows, generator=g) > 0).long()
+    elif args.objective_hint == "rank":
+        # a 0-4 relevance grade: the noisy target cut at fixed levels
+        y = torch.bucketize(logit + 0.5 * torch.randn(args.rows, generator=g), torch.tensor(RANK_GRADE_CUTS))
     else:
         y = logit + 0.1 * torch.randn(args.rows, generator=g)
     return X, y
+
+
+RANK_GRADE_CUTS = [-3.5, -1.8, -0.6, 0.6]
+
+
+def load_groups(args, rank: int) -> torch.Tensor:
+    """The query group sizes of the rank's synthetic rows (``--objective_hint rank``): drawn
+    uniformly from [group_size / 2, 3 group_size / 2] with a fixed seed until they cover
+    ``--rows``, the last one cut to fit -- every rank holds whole groups."""
+    g = torch.Generator().manual_seed(4321 + rank)
+    lo, hi = max(args.group_size // 2, 1), max(args.group_size * 3 // 2, 1)
+    sizes = torch.randint(lo, hi + 1, (args.rows // lo + 1,), generator=g)
+    ends = torch.cumsum(sizes, 0)
+    q = int(torch.searchsorted(ends, args.rows))  # the first group that reaches the last row
+    sizes = sizes[:q + 1].clone()
+    sizes[q] -= int(ends[q]) - args.rows
+    return sizes[sizes > 0]
 
 
 def model_file(args) -> str:
@@ -98,9 +123,15 @@ def run_predict(args, info) -> int:
         args.dataset = "iris" if model.p.objective.startswith("multi:") else "synthetic"
         if args.dataset == "synthetic" and model.cuts is not None:
             args.features = int(model.cuts.shape[0])
+    ranking = model.p.objective.startswith("rank:")
+    if ranking and args.dataset != "synthetic":
+        print("xgboost_dist: a ranking model predicts --dataset synthetic (the groups are generated)",
+              file=sys.stderr, flush=True)
+        return 2
     if not model.p.objective.startswith(("multi:", "binary:")):
-        args.objective_hint = "reg"
+        args.objective_hint = "rank" if ranking else "reg"
     X, y = load_data(args, info.rank, info.world_size)
+    met_kw = {"group": load_groups(args, info.rank)} if ranking else {}  # the groups a Train run of these rows had
     X = X.to(info.device)
 
     def sync():
@@ -116,7 +147,7 @@ def run_predict(args, info) -> int:
     out_path = f"{path}.pred.rank{info.rank}.npy"
     np.save(out_path, pred.cpu().numpy())
     common.report_progress(1, final=True)
-    met = model.metric(margin, y.to(info.device))
+    met = model.metric(margin, y.to(info.device), **met_kw)
     extra = {}
     if args.pred_contribs:
         # the background is every rank's shard: set_background all-reduces the covers
@@ -157,7 +188,8 @@ def main(argv=None) -> int:
     ap.add_argument("--dataset", default=None, choices=[None, "iris", "synthetic"])
     ap.add_argument("--rows", type=int, default=200000)
     ap.add_argument("--features", type=int, default=28)
-    ap.add_argument("--objective_hint", default="binary", choices=["binary", "reg"])
+    ap.add_argument("--objective_hint", default="binary", choices=["binary", "reg", "rank"])
+    ap.add_argument("--group_size", type=int, default=100)
     ap.add_argument("--cpu", action="store_true")
     ap.add_argument("--eval_fraction", type=float, default=0.0)
     ap.add_argument("--early_stopping_rounds", type=int, default=0)
@@ -178,7 +210,7 @@ def main(argv=None) -> int:
         return rc
     if args.dataset is None:
         args.dataset = "iris" if "num_class:3" in args.xgboost_parameter else "synthetic"
-    default_obj = "binary:logistic" if args.objective_hint == "binary" else "reg:squarederror"
+    default_obj = {"binary": "binary:logistic", "rank": "rank:ndcg"}.get(args.objective_hint, "reg:squarederror")
     params = GBDTParams.parse(args.xgboost_parameter or f"objective:{default_obj}",
                               n_estimators=args.n_estimators, learning_rate=args.learning_rate,
                               max_depth=args.max_depth, max_bin=args.max_bin)
@@ -186,9 +218,27 @@ def main(argv=None) -> int:
         params.max_bin = 64
     if args.early_stopping_rounds > 0:
         params.early_stopping_rounds = args.early_stopping_rounds
+    ranking = params.objective.startswith("rank:")
+    if ranking and (args.dataset != "synthetic" or args.objective_hint != "rank"):
+        print(f"xgboost_dist: {params.objective} trains on --dataset synthetic --objective_hint rank",
+              file=sys.stderr, flush=True)
+        kdist.shutdown(info)
+        return 2
     X, y = load_data(args, info.rank, info.world_size)
-    fit_kw = {}
-    if args.eval_fraction > 0:
+    fit_kw, met_kw = {}, {}
+    if ranking:
+        sizes = load_groups(args, info.rank)
+        if args.eval_fraction > 0:
+            # every round(1 / fraction)-th group of the shard is held out, whole
+            step = max(int(round(1.0 / args.eval_fraction)), 2)
+            held_q = torch.zeros(sizes.numel(), dtype=torch.bool)
+            held_q[step - 1::step] = True
+            held = torch.repeat_interleave(held_q, sizes)
+            fit_kw = {"eval_set": (X[held].contiguous(), y[held].contiguous(), sizes[held_q]),
+                      "early_stopping_rounds": params.early_stopping_rounds}
+            X, y, sizes = X[~held].contiguous(), y[~held].contiguous(), sizes[~held_q]
+        fit_kw["group"] = met_kw["group"] = sizes
+    elif args.eval_fraction > 0:
         # every round(1 / fraction)-th row of the shard is held out
         step = max(int(round(1.0 / args.eval_fraction)), 2)
         held = torch.zeros(X.shape[0], dtype=torch.bool)
@@ -203,9 +253,9 @@ def main(argv=None) -> int:
     if info.device.type == "cuda":
         torch.cuda.synchronize()
     dt = kdist.all_reduce_max(time.perf_counter() - t0, info)
-    met = model.metric(pred, y.to(info.device))
+    met = model.metric(pred, y.to(info.device), **met_kw)
     rounds = len(model.trees)  # < n_estimators after an early stop
-    if fit_kw:
+    if "eval_set" in fit_kw:
         common.report_progress(rounds, final=True)
     out = {"job_type": "Train", "rank": info.rank, "world_size": info.world_size, "objective": params.objective,
            "rounds": rounds, "rows_per_rank": int(X.shape[0]), "features": int(X.shape[1]),
@@ -214,7 +264,7 @@ def main(argv=None) -> int:
            "rounds_per_sec": (rounds / model.stats["boost_s"]
                               if model.stats.get("boost_s", 0) > 0 else 0.0),
            "device": str(info.device), "hip_kernels": model.use_hip, **met, **model.stats}
-    if fit_kw:
+    if "eval_set" in fit_kw:
         out.update({"eval_rows": int(fit_kw["eval_set"][0].shape[0]), "eval_metric": model.eval_metric,
                     "eval_last": model.evals_result[-1] if model.evals_result else None,
                     "best_iteration": model.best_iteration, "best_score": model.best_score})
