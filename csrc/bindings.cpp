@@ -270,6 +270,44 @@ void adam_step(const at::Tensor& chunks, at::Tensor master, at::Tensor m1, at::T
             "fused_adam");
 }
 
+// meta: int64 [n, 2] rows (first | count << 32, tensor) beside ``chunks``; part: fp32 [2 n] scratch;
+// trust: fp32 [tensors], written (one ratio per tensor, 1 outside group 0)
+void lars_step(const at::Tensor& chunks, const at::Tensor& meta, at::Tensor part, at::Tensor master,
+               at::Tensor mom, const at::Tensor& grad, at::Tensor param, at::Tensor trust, double lr,
+               double momentum, double wd, double eta, double eps, double grad_scale, bool first_step) {
+  check_chunks(chunks);
+  static_assert(sizeof(kdl::LarsChunk) == 16, "LarsChunk layout");
+  const int64_t n = chunks.size(0);
+  TORCH_CHECK(meta.is_cuda() && meta.scalar_type() == at::kLong && meta.dim() == 2 && meta.size(0) == n &&
+                  meta.size(1) == 2 && meta.is_contiguous() && chunks.is_contiguous(),
+              "lars_step: meta must be an int64 [n, 2] GPU tensor beside the chunk table");
+  TORCH_CHECK(part.is_cuda() && part.scalar_type() == at::kFloat && part.is_contiguous() && part.numel() >= 2 * n,
+              "lars_step: part must be an fp32 GPU tensor of >= 2 n elements");
+  TORCH_CHECK(trust.is_cuda() && trust.scalar_type() == at::kFloat && trust.is_contiguous() && trust.numel() > 0,
+              "lars_step: trust must be an fp32 GPU tensor, one element per tensor");
+  TORCH_CHECK(master.scalar_type() == at::kFloat && mom.scalar_type() == at::kFloat,
+              "lars_step: master/momentum must be fp32");
+  TORCH_CHECK(master.numel() == grad.numel() && grad.numel() == param.numel() &&
+                  mom.numel() == master.numel(),
+              "lars_step: flat buffer size mismatch");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(master.device());
+  kdl::LarsHyper h{};
+  h.lr = static_cast<float>(lr);
+  h.momentum = static_cast<float>(momentum);
+  h.wd = static_cast<float>(wd);
+  h.eta = static_cast<float>(eta);
+  h.eps = static_cast<float>(eps);
+  h.grad_scale = static_cast<float>(grad_scale);
+  h.first_step = first_step;
+  check_hip(kdl::fused_lars(reinterpret_cast<const kdl::OptChunk*>(chunks.data_ptr<int64_t>()),
+                            reinterpret_cast<const kdl::LarsChunk*>(meta.data_ptr<int64_t>()),
+                            static_cast<int>(n), part.data_ptr<float>(), master.data_ptr<float>(),
+                            mom.data_ptr<float>(), grad.data_ptr(), param.data_ptr(),
+                            trust.data_ptr<float>(), dtype_code(grad), dtype_code(param), h,
+                            cur_stream()),
+            "fused_lars");
+}
+
 at::Tensor chunk_sumsq(const at::Tensor& chunks, const at::Tensor& x, double scale) {
   check_chunks(chunks);
   const c10::hip::HIPGuardMasqueradingAsCUDA guard(x.device());
@@ -1244,8 +1282,10 @@ void need_f32(const at::Tensor& t, int64_t numel, const char* what) {
 
 // x [Nb, C, H, W] channels_last (the last block's output); ws = (feat, part1, lrow, dl, dlT)
 void head_forward(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& b, const at::Tensor& y,
-                  at::Tensor feat, at::Tensor part1, at::Tensor lrow, at::Tensor dl, at::Tensor dlT) {
+                  at::Tensor feat, at::Tensor part1, at::Tensor lrow, at::Tensor dl, at::Tensor dlT,
+                  double label_smoothing) {
   TORCH_CHECK(x.dim() == 4 && is_nhwc_dense(x), "head_forward: x must be [Nb, C, H, W] channels_last");
+  TORCH_CHECK(label_smoothing >= 0.0 && label_smoothing < 1.0, "head_forward: label_smoothing in [0, 1)");
   const int64_t Nb = x.size(0), C = x.size(1), HW = x.size(2) * x.size(3);
   TORCH_CHECK(w.dim() == 2 && w.size(1) == C && w.is_contiguous(), "head_forward: w must be [L, C] contiguous");
   const int64_t L = w.size(0);
@@ -1265,7 +1305,7 @@ void head_forward(const at::Tensor& x, const at::Tensor& w, const c10::optional<
   check_hip(kdl::head_forward(x.data_ptr(), static_cast<int>(Nb), static_cast<int>(HW), static_cast<int>(C),
                               w.data_ptr(), opt_ptr(b), static_cast<int>(L), y.data_ptr<int64_t>(), feat.data_ptr(),
                               part1.data_ptr<float>(), lrow.data_ptr<float>(), dl.data_ptr(), dlT.data_ptr(),
-                              cur_stream()),
+                              cur_stream(), static_cast<float>(label_smoothing)),
             "head_forward");
 }
 
@@ -2206,6 +2246,7 @@ PYBIND11_MODULE(_C, m) {
   m.def("sgd_step", &sgd_step, "flat chunked fused SGD-momentum with fp32 master weights");
   m.def("adam_step", &adam_step, "flat chunked fused Adam/AdamW with fp32 master weights");
   m.def("chunk_sumsq", &chunk_sumsq, "per-chunk sum of squares");
+  m.def("lars_step", &lars_step, "flat chunked fused LARS: per-chunk norm partials, then trust ratio + momentum update");
   m.def("cast_copy", &cast_copy, "flat dtype-casting copy");
   m.def("transpose_tiles", &transpose_tiles, "batched bf16 2-D transposes from a static 64x64 tile table");
   m.def("ipc_handle", &ipc_handle, "(IPC handle bytes, byte offset) of a GPU tensor's allocation");
@@ -2307,7 +2348,9 @@ PYBIND11_MODULE(_C, m) {
         "fp32 slab count of stem7x7_wgrad's workspace", py::arg("nb"), py::arg("h") = 224, py::arg("w") = 224);
   m.def("head_splits", &head_splits, "K splits (fc forward, dfeat) of the classifier head kernels");
   m.def("head_lpad", [](int64_t L) { return kdl::head_lpad(static_cast<int>(L)); }, "row pitch of the head's dl");
-  m.def("head_forward", &head_forward, "classifier head forward: mean pool + fc (MFMA) + softmax CE + dlogits");
+  m.def("head_forward", &head_forward, "classifier head forward: mean pool + fc (MFMA) + softmax CE + dlogits",
+        py::arg("x"), py::arg("w"), py::arg("b"), py::arg("y"), py::arg("feat"), py::arg("part1"), py::arg("lrow"),
+        py::arg("dl"), py::arg("dlT"), py::arg("label_smoothing") = 0.0);
   m.def("head_backward", &head_backward, "classifier head backward: dfeat, dW, db (MFMA) + mean loss");
   m.def("stem7x7_fwd", &stem7x7_fwd, "ResNet stem 7x7/s2/p3 conv (224 -> 112, 3 -> 64 channels) with BN statistics epilogue");
   m.def("conv3x3_s2_dgrad", &conv3x3_s2_dgrad,

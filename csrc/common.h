@@ -14,6 +14,10 @@
     if (_e != hipSuccess) return _e;                                              \
   } while (0)
 
+// On a kernel: plain fp32 ops only, no packed v_pk_*_f32 pairs (the per-function
+// form of the -packed-fp32-ops file flag of ops/build.py).
+#define PLAIN_F32_KERNEL __attribute__((target("no-packed-fp32-ops")))
+
 namespace kdl {
 
 constexpr int kWave = 64;

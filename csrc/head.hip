@@ -220,10 +220,15 @@ __device__ __forceinline__ float block_reduce(float v, float* red, bool is_max) 
   return r;
 }
 
+// SMOOTH: label smoothing eps, targets (1 - eps) onehot + eps / L:
+//   loss_n = lse - (1 - eps) z[y] - (eps / L) sum_l z[l]   (one more block sum over the LDS row)
+//   dl     = (softmax - (1 - eps) onehot - eps / L) * inv_n
+// eps == 0 launches the plain instantiation (head_forward): its code is the kernel as it was.
+template <bool SMOOTH>
 __global__ __launch_bounds__(256) void head_ce_kernel(const float* __restrict__ part1, int splits, int Nb, int L,
                                                       int Lp,
                                                       const bf16_t* __restrict__ bias,
-                                                      const int64_t* __restrict__ y, float inv_n,
+                                                      const int64_t* __restrict__ y, float inv_n, float eps,
                                                       float* __restrict__ lrow, bf16_t* __restrict__ dl,
                                                       bf16_t* __restrict__ dlT) {
   extern __shared__ float z[];  // [L]
@@ -240,16 +245,31 @@ __global__ __launch_bounds__(256) void head_ce_kernel(const float* __restrict__ 
   float se = 0.f;
   for (int l = t; l < L; l += 256) se += __expf(z[l] - mx);
   se = block_reduce(se, red, false);
+  float sz = 0.f;
+  if (SMOOTH) {
+    for (int l = t; l < L; l += 256) sz += z[l];
+    sz = block_reduce(sz, red, false);
+  }
+  const float hot = 1.f - eps, unif = eps / static_cast<float>(L);  // SMOOTH only
   const int64_t y64 = y[n];
   // a label outside [0, L) (e.g. an ignore_index of -100) never indexes z: its
   // row's loss is NaN -- the step's mean loss turns NaN, loudly, as the
   // autograd head would have raised -- and its gradient row is zero
   const bool ok = y64 >= 0 && y64 < L;
   const int yn = ok ? static_cast<int>(y64) : -1;
-  if (t == 0) lrow[n] = ok ? __logf(se) + mx - z[yn] : __int_as_float(0x7fc00000);
+  if (t == 0) {
+    if (SMOOTH)
+      lrow[n] = ok ? __logf(se) + mx - hot * z[yn] - unif * sz : __int_as_float(0x7fc00000);
+    else
+      lrow[n] = ok ? __logf(se) + mx - z[yn] : __int_as_float(0x7fc00000);
+  }
   const float rse = 1.f / se;
   for (int l = t; l < Lp; l += 256) {  // dl rows padded to Lp (16-B rows for the backward's loads)
-    const float g = (l < L && ok) ? (__expf(z[l] - mx) * rse - (l == yn ? 1.f : 0.f)) * inv_n : 0.f;
+    float g;
+    if (SMOOTH)
+      g = (l < L && ok) ? (__expf(z[l] - mx) * rse - (l == yn ? hot : 0.f) - unif) * inv_n : 0.f;
+    else
+      g = (l < L && ok) ? (__expf(z[l] - mx) * rse - (l == yn ? 1.f : 0.f)) * inv_n : 0.f;
     const bf16_t gb = f32_to_bf16(g);
     dl[static_cast<int64_t>(n) * Lp + l] = gb;
     if (l < L) dlT[static_cast<int64_t>(l) * Nb + n] = gb;
@@ -369,8 +389,10 @@ void head_splits(int Nb, int C, int L, int* s1, int* s2) {
 }
 
 hipError_t head_forward(const void* x, int Nb, int HW, int C, const void* w, const void* b, int L, const int64_t* y,
-                        void* feat, float* part1, float* lrow, void* dl, void* dlT, hipStream_t s) {
+                        void* feat, float* part1, float* lrow, void* dl, void* dlT, hipStream_t s,
+                        float label_smoothing) {
   if (Nb <= 0 || HW <= 0 || C % 8 || L <= 0 || L > 8192) return hipErrorInvalidValue;
+  if (!(label_smoothing >= 0.f && label_smoothing < 1.f)) return hipErrorInvalidValue;
   int s1, s2;
   head_splits(Nb, C, L, &s1, &s2);
   hipLaunchKernelGGL(head_pool_kernel, dim3(Nb, (C + 511) / 512), dim3(256), 0, s, static_cast<const bf16_t*>(x), HW,
@@ -379,9 +401,14 @@ hipError_t head_forward(const void* x, int Nb, int HW, int C, const void* w, con
   g.part = part1;
   HeadGemm none{};
   hipLaunchKernelGGL((head_gemm_kernel<false, false>), dim3(g.blocks), dim3(256), 0, s, g, none);
-  hipLaunchKernelGGL(head_ce_kernel, dim3(Nb), dim3(256), L * sizeof(float), s, part1, s1, Nb, L, head_lpad(L),
-                     static_cast<const bf16_t*>(b), y, 1.f / static_cast<float>(Nb), lrow, static_cast<bf16_t*>(dl),
-                     static_cast<bf16_t*>(dlT));
+  if (label_smoothing > 0.f)
+    hipLaunchKernelGGL(head_ce_kernel<true>, dim3(Nb), dim3(256), L * sizeof(float), s, part1, s1, Nb, L,
+                       head_lpad(L), static_cast<const bf16_t*>(b), y, 1.f / static_cast<float>(Nb), label_smoothing,
+                       lrow, static_cast<bf16_t*>(dl), static_cast<bf16_t*>(dlT));
+  else
+    hipLaunchKernelGGL(head_ce_kernel<false>, dim3(Nb), dim3(256), L * sizeof(float), s, part1, s1, Nb, L,
+                       head_lpad(L), static_cast<const bf16_t*>(b), y, 1.f / static_cast<float>(Nb), 0.f, lrow,
+                       static_cast<bf16_t*>(dl), static_cast<bf16_t*>(dlT));
   return hipGetLastError();
 }
 

@@ -111,6 +111,30 @@ hipError_t fused_adam(const OptChunk* chunks, int nchunks, float* master, float*
                       hipStream_t s);
 hipError_t chunk_sumsq(const OptChunk* chunks, int nchunks, const void* x, int dtype, float scale,
                        float* out, hipStream_t s);
+// LARS: per chunk, where its tensor's chunks lie in the chunk table (they are
+// contiguous) and the tensor's index into ``trust``.
+struct LarsChunk {
+  int32_t first;
+  int32_t count;
+  int32_t tensor;
+  int32_t pad;
+};
+struct LarsHyper {
+  float lr;
+  float momentum;
+  float wd;  // group 0 only; the other groups are neither decayed nor adapted
+  float eta;
+  float eps;
+  float grad_scale;
+  int first_step;
+};
+// Two launches: part[2][nchunks] = per-chunk sum g^2 | sum w^2 (group 0), then
+// the update with trust = eta |w| / (|g| + wd |w| + eps) per group-0 tensor
+// (1 where either norm is 0), v = momentum v + lr trust (g + wd w), w -= v;
+// trust[tensor] is also stored.  g = grad * grad_scale throughout.
+hipError_t fused_lars(const OptChunk* chunks, const LarsChunk* meta, int nchunks, float* part,
+                      float* master, float* mom, const void* grad, void* param, float* trust,
+                      int gdtype, int pdtype, const LarsHyper& h, hipStream_t s);
 // ---- multi_tensor.hip
 struct PackChunk {
   int32_t tensor;  // index into the per-step source pointer table
@@ -491,7 +515,8 @@ hipError_t head_eval(const void* x, int Nb, int HW, int C, const void* w, const 
                      hipStream_t s);
 int head_lpad(int L);  // dl's row pitch: L rounded up to 8
 hipError_t head_forward(const void* x, int Nb, int HW, int C, const void* w, const void* b, int L, const int64_t* y,
-                        void* feat, float* part1, float* lrow, void* dl, void* dlT, hipStream_t s);
+                        void* feat, float* part1, float* lrow, void* dl, void* dlT, hipStream_t s,
+                        float label_smoothing = 0.f);  // eps in [0, 1): targets (1 - eps) onehot + eps / L
 hipError_t head_backward(const void* feat, const void* w, const void* dl, const void* dlT, int Nb, int C, int L,
                          float* part2, void* dfeat, void* dW, void* db, const float* lrow, float* loss,
                          hipStream_t s);

@@ -547,9 +547,10 @@ class HipKernels:
                 and fmap.is_contiguous(memory_format=torch.channels_last) and n % 8 == 0 and c % 8 == 0
                 and L <= 8192 and y.dtype == torch.int64)
 
-    def head(self, fmap, w, b, y, dw, db):
+    def head(self, fmap, w, b, y, dw, db, label_smoothing: float = 0.0):
         """Pool -> fc -> softmax CE -> backward on csrc/head.hip: (loss [1],
-        dfeat [n, c] bf16); dW / db written into ``dw`` / ``db``."""
+        dfeat [n, c] bf16); dW / db written into ``dw`` / ``db``.
+        ``label_smoothing`` > 0: the smoothed instantiation of the CE kernel."""
         n, c = fmap.shape[:2]
         L = w.shape[0]
         key = ("head", n, c, L)
@@ -563,7 +564,8 @@ class HipKernels:
                                         dlT=torch.empty(L, n, **bf), part2=torch.empty(s2 * n * c, **f32),
                                         dfeat=torch.empty(n, c, **bf))
         yc = y if y.is_contiguous() else y.contiguous()
-        self.ext.head_forward(fmap, w, b, yc, ws["feat"], ws["part1"], ws["lrow"], ws["dl"], ws["dlT"])
+        self.ext.head_forward(fmap, w, b, yc, ws["feat"], ws["part1"], ws["lrow"], ws["dl"], ws["dlT"],
+                              float(label_smoothing))
         loss = torch.empty(1, dtype=torch.float32, device=fmap.device)  # fresh per step (returned)
         self.ext.head_backward(ws["feat"], w, ws["dl"], ws["dlT"], ws["part2"], ws["dfeat"], dw, db, ws["lrow"],
                                loss)
@@ -975,8 +977,9 @@ class ResNetEngine:
     called once that gradient is final (DP bucket launch)."""
 
     def __init__(self, model: ResNet, backend: str = "auto", grad_view=None, on_ready=None,
-                 options: EngineOptions | None = None, side=None):
+                 options: EngineOptions | None = None, side=None, label_smoothing: float = 0.0):
         self.model = model
+        self.label_smoothing = float(label_smoothing)  # training loss only: evaluation is the plain CE
         p = next(model.parameters())
         self.dev = p.device
         if backend == "auto":
@@ -1305,7 +1308,8 @@ class ResNetEngine:
         if head is not None and self.K.head_ok(feat_map, m.fc.weight, y):
             # csrc/head.hip: pool + fc + softmax CE + their backward, dW / db straight
             # into the gradient buffer (no autograd, no vendor GEMM)
-            loss, dfeat = head(feat_map, m.fc.weight, m.fc.bias, y, self._g(m.fc.weight), self._g(m.fc.bias))
+            loss, dfeat = head(feat_map, m.fc.weight, m.fc.bias, y, self._g(m.fc.weight), self._g(m.fc.bias),
+                               self.label_smoothing)
             self.on_ready(m.fc.weight)
             self.on_ready(m.fc.bias)
             self.backward(dfeat, h * w)
@@ -1315,7 +1319,7 @@ class ResNetEngine:
             fcw = m.fc.weight.detach().requires_grad_(True)
             fcb = m.fc.bias.detach().requires_grad_(True)
             logits = F.linear(feat.to(fcw.dtype), fcw, fcb)
-            loss = F.cross_entropy(logits.float(), y)
+            loss = F.cross_entropy(logits.float(), y, label_smoothing=self.label_smoothing)
             dfeat, dfcw, dfcb = torch.autograd.grad(loss, (feat, fcw, fcb))
         with torch.no_grad():
             self._g(m.fc.weight).copy_(dfcw)

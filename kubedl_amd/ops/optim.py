@@ -1,4 +1,4 @@
-"""Flat parameter space + fused SGD / Adam(W) driven by ``csrc/optim.hip``.
+"""Flat parameter space + fused SGD / Adam(W) / LARS driven by ``csrc/optim.hip``.
 
 ``FlatParamSpace`` relocates every trainable parameter of a module into one
 flat buffer (``param``, model dtype, typically bf16) and points each ``.grad``
@@ -9,7 +9,7 @@ at a view of one flat gradient buffer (``grad``).  Consequences:
   flatten/unflatten copies on the critical path;
 * the optimizer is ONE kernel launch over a precomputed chunk table, with an
   fp32 master copy and fp32 state, and writes the bf16 model weights in the
-  same pass.
+  same pass (``FusedLARS``: two launches, the first for the per-tensor norms).
 
 Layout order is reverse registration order (~ the order backward produces
 gradients), each region aligned to 64 elements (128 B in bf16) and padded
@@ -361,3 +361,77 @@ class FusedAdam(_FusedBase):
         denom = (self.m2.sqrt() / math.sqrt(bc2)).add_(self.eps)
         sp.master.addcdiv_(self.m1, denom, value=-self.lr / bc1)
         sp.param.copy_(sp.master)
+
+
+class FusedLARS(_FusedBase):
+    """LARS (layer-wise adaptive rate scaling) with momentum over the flat space: two
+    launches of csrc/optim.hip (per-chunk norm partials, then the update), no host sync.
+
+    For a parameter tensor ``t`` of group 0 (``ParamSlot.group == 0``, the decayed weights),
+    with ``g = grad * grad_scale``, ``wn = ||w_t||_2`` over the fp32 master, ``gn = ||g_t||_2``::
+
+        trust_t = eta * wn / (gn + wd * wn + eps)   if wn > 0 and gn > 0 else 1
+        u = g + wd * w
+        v = momentum * v + (lr * trust_t) * u
+        w = w - v
+
+    For group 1 (BN affine parameters and biases) there is neither decay nor adaptation:
+    ``v = momentum * v + lr * g``, ``w = w - v``.  On the first step ``v`` is not read (taken
+    as 0).  The bf16 / fp32 ``param`` is written from the new ``w`` in the same pass.
+
+    ``lr``, ``eta``, ``weight_decay`` and ``momentum`` are kernel arguments: a schedule sets
+    ``opt.lr`` between steps without a device write.  ``trust`` holds the last step's ratio
+    of every slot (1 for group 1), in ``space.slots`` order; ``mom`` is the momentum state."""
+
+    def __init__(self, space: FlatParamSpace, lr: float, momentum: float = 0.9, weight_decay: float = 0.0,
+                 eta: float = 0.001, eps: float = 1e-9):
+        super().__init__(space, lr, weight_decay)
+        self.momentum = momentum
+        self.eta = eta
+        self.eps = eps
+        self.mom = torch.zeros_like(space.master)
+        self.trust = torch.ones(len(space.slots), dtype=torch.float32, device=space.device)
+        self.meta_cpu = self._meta_table()
+        self.meta = self.meta_cpu.to(space.device)
+        self._part = torch.zeros(2 * self.meta_cpu.shape[0], dtype=torch.float32, device=space.device)
+
+    def _meta_table(self) -> torch.Tensor:
+        """Beside ``space.chunks``: per chunk its tensor's (first chunk | chunk count << 32, slot index);
+        a slot's chunks are consecutive rows of the chunk table."""
+        sp = self.space
+        rows = []
+        for t, s in enumerate(sp.slots):
+            count = -(-_round_up(s.numel, 8) // sp.chunk)
+            first = len(rows)
+            rows += [(first | (count << 32), t)] * count
+        assert len(rows) == sp.chunks_cpu.shape[0]
+        return torch.tensor(rows, dtype=torch.int64)
+
+    @torch.no_grad()
+    def step(self) -> None:
+        sp = self.space
+        sp.pack_grads()
+        first = self.step_count == 0
+        if self._use_hip():
+            _ext.load().lars_step(sp.chunks, self.meta, self._part, sp.master, self.mom, sp.grad, sp.param,
+                                  self.trust, float(self.lr), float(self.momentum), float(self.weight_decay),
+                                  float(self.eta), float(self.eps), float(self.grad_scale), bool(first))
+        else:
+            for t, s in enumerate(sp.slots):
+                sl = slice(s.offset, s.offset + s.numel)
+                w, v = sp.master[sl], self.mom[sl]
+                g = sp.grad[sl].float() * self.grad_scale
+                rate = self.lr
+                if s.group == 0:
+                    wn, gn = float(w.double().norm()), float(g.double().norm())
+                    trust = self.eta * wn / (gn + self.weight_decay * wn + self.eps) if wn > 0 and gn > 0 else 1.0
+                    self.trust[t] = trust
+                    rate = self.lr * trust
+                    g = g + self.weight_decay * w
+                if first:
+                    v.copy_(g * rate)
+                else:
+                    v.mul_(self.momentum).add_(g, alpha=rate)
+                w.sub_(v)
+            sp.param.copy_(sp.master)
+        self.step_count += 1

@@ -31,6 +31,13 @@ instead of the one synthetic batch, ``--data-eval DIR`` evaluates on one, and
 ``eval_dropped``.  A resumed job reads the batches of its own steps: the batch
 of a step is a pure function of (seed, step, rank, world, batch).  Without
 ``--data`` nothing changes.
+
+``--optimizer lars`` replaces the SGD launch with ``FusedLARS`` (two launches:
+per-chunk norm partials, then the trust-ratio update); ``--lr-schedule`` /
+``--lr-warmup-steps`` make the rate a function of the step index
+(``ops/lr_schedule.py``), passed as a kernel argument; ``--label-smoothing``
+smooths the training loss in the head kernel.  The defaults (``sgd``, constant
+0.1, no smoothing) are the run the worker always did.
 """
 from __future__ import annotations
 
@@ -50,7 +57,8 @@ import torch.distributed as dist  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
 from kubedl_amd.models.resnet import resnet50, resnet_tiny  # noqa: E402
-from kubedl_amd.ops.optim import FlatParamSpace, FusedSGD
+from kubedl_amd.ops.lr_schedule import KINDS as LR_KINDS, lr_at
+from kubedl_amd.ops.optim import FlatParamSpace, FusedLARS, FusedSGD
 from kubedl_amd.parallel import dist as kdist
 from kubedl_amd.parallel.ddp import FlatDDP
 from kubedl_amd.utils.checkpoint import Checkpointer
@@ -68,8 +76,19 @@ class ResNetTrainer:
                  momentum: float = 0.9, weight_decay: float = 5e-5, tiny: bool = False,
                  bn_backend: str = "auto", bucket_cap_mb: float = 12.0, seed: int = 0,
                  conv_benchmark: bool = False, engine: str = "auto", on_streams_ready=None,
-                 before_collectives=None, train_input=None):
-        """``engine``: "fused" runs the step through ``models.resnet_engine``
+                 before_collectives=None, train_input=None, optimizer: str = "sgd", lars_eta: float = 0.001,
+                 label_smoothing: float = 0.0, lr_schedule: str = "constant", lr_warmup_steps: int = 0,
+                 lr_total_steps: int = 0, lr_end: float = 0.0, lr_power: float = 2.0):
+        """``optimizer``: "sgd" (``FusedSGD``) or "lars" (``FusedLARS`` with trust coefficient
+        ``lars_eta``), both with ``lr`` / ``momentum`` / ``weight_decay``.  ``lr`` is the peak
+        of ``ops.lr_schedule.lr_at``: ``lr_schedule`` ("constant", "poly", "cosine") after
+        ``lr_warmup_steps`` of linear warm-up, decaying to ``lr_end`` at ``lr_total_steps``
+        (an attribute: the worker sets it once the job's length is known).  The rate of a step
+        depends on the step index alone, so a resumed job continues on the right one; "constant"
+        without warm-up never touches ``opt.lr``.  ``label_smoothing``: of the training loss
+        (csrc/head.hip's smoothed kernel); evaluation reports the plain cross-entropy.
+
+        ``engine``: "fused" runs the step through ``models.resnet_engine``
         (fused 1x1-conv GEMMs + staged BN, explicit backward); "autograd" runs
         the module under autograd; "auto" = fused on the GPU when the model's
         channel counts fit the GEMM tiles (multiples of 64), else autograd.
@@ -149,10 +168,23 @@ class ResNetTrainer:
             from kubedl_amd.models.resnet_engine import ResNetEngine
             self.engine = ResNetEngine(model, backend="hip" if dev.type == "cuda" else "torch",
                                        grad_view=self.space.grad_view, on_ready=self.ddp.ready, options=eopts,
-                                       side=side)
+                                       side=side, label_smoothing=label_smoothing)
             self.ddp.join_stream = self.engine.side
-        self.opt = FusedSGD(self.space, lr=lr, momentum=momentum, weight_decay=weight_decay)
+        if optimizer == "sgd":
+            self.opt = FusedSGD(self.space, lr=lr, momentum=momentum, weight_decay=weight_decay)
+        elif optimizer == "lars":
+            self.opt = FusedLARS(self.space, lr=lr, momentum=momentum, weight_decay=weight_decay, eta=lars_eta)
+        else:
+            raise ValueError(f"optimizer {optimizer!r}: sgd or lars")
         self.opt.grad_scale = self.ddp.grad_scale
+        self.label_smoothing = float(label_smoothing)
+        self.peak_lr = lr
+        self.lr_schedule = lr_schedule
+        self.lr_warmup_steps = lr_warmup_steps
+        self.lr_total_steps = lr_total_steps
+        self.lr_end = lr_end
+        self.lr_power = lr_power
+        lr_at(0, peak=lr, kind=lr_schedule)  # an unknown kind fails here, not in step 1
         # synthetic batch, generated where it is used (no 77 MB host->device copy)
         g = torch.Generator(device=dev).manual_seed(seed + 1000 + info.rank)
         if dev.type == "cuda":
@@ -220,6 +252,11 @@ class ResNetTrainer:
         """The step's device work: returns the loss."""
         if self.input is not None:
             self.x, self.y = self.input.next(self.steps_done)
+        if self.lr_schedule != "constant" or self.lr_warmup_steps > 0:
+            # a kernel argument of the optimizer launch: no device write, no sync
+            self.opt.lr = lr_at(self.steps_done, peak=self.peak_lr, kind=self.lr_schedule,
+                                warmup_steps=self.lr_warmup_steps, total_steps=self.lr_total_steps,
+                                end_lr=self.lr_end, power=self.lr_power)
         self.steps_done += 1
         self.space.zero_grad()
         with trace_range("forward_backward"):
@@ -228,7 +265,7 @@ class ResNetTrainer:
                 self.space.mark_packed()  # gradients were written into the flat buffer
             else:
                 out = self.model(self.x)
-                loss = F.cross_entropy(out.float(), self.y)
+                loss = F.cross_entropy(out.float(), self.y, label_smoothing=self.label_smoothing)
                 loss.backward()
         with trace_range("allreduce_wait"):
             self.ddp.finish()
@@ -363,7 +400,10 @@ def run(args) -> dict:
     if train_shards is not None or eval_shards is not None:
         kw["num_classes"] = max(s.classes for s in (train_shards, eval_shards) if s is not None)
     tr = ResNetTrainer(info, batch=args.batch, image=args.image, tiny=args.tiny,
-                       bn_backend=args.bn_backend, engine=args.engine, **kw)
+                       bn_backend=args.bn_backend, engine=args.engine, lr=args.lr, momentum=args.momentum,
+                       weight_decay=args.weight_decay, optimizer=args.optimizer, lars_eta=args.lars_eta,
+                       label_smoothing=args.label_smoothing, lr_schedule=args.lr_schedule,
+                       lr_warmup_steps=args.lr_warmup_steps, lr_end=args.lr_end, **kw)
     E = max(args.eval_batches, 0)
 
     def shard_input(shards, train, max_batches=0):
@@ -388,6 +428,8 @@ def run(args) -> dict:
         tr.load_state_dict(st)
         tr.steps_done = done  # the input continues at the step's own batches (data/plan.py)
     total = args.warmup + args.steps
+    # the schedule spans the job's own steps (timing warm-up included) unless told otherwise
+    tr.lr_total_steps = args.lr_total_steps if args.lr_total_steps is not None else total
     dstats = {}
     if eval_in is not None:
         dstats["eval_dropped"] = eval_in.dropped
@@ -528,6 +570,21 @@ def build_parser() -> argparse.ArgumentParser:
                          "KDL_HBM_LIMIT_GB slice)")
     ap.add_argument("--data-workers", type=int, default=4, help="gather threads of --data-mode stream")
     ap.add_argument("--data-seed", type=int, default=0, help="seed of the image order and the crop boxes")
+    ap.add_argument("--optimizer", default="sgd", choices=["sgd", "lars"],
+                    help="lars: layer-wise trust ratios on the decayed weights (two fused launches, csrc/optim.hip)")
+    ap.add_argument("--lr", type=float, default=0.1, help="learning rate (the schedule's peak)")
+    ap.add_argument("--momentum", type=float, default=0.9)
+    ap.add_argument("--weight-decay", type=float, default=5e-5, help="on the conv / fc weights, not BN or biases")
+    ap.add_argument("--lars-eta", type=float, default=0.001, help="LARS trust coefficient")
+    ap.add_argument("--lr-schedule", default="constant", choices=list(LR_KINDS),
+                    help="decay after the learning-rate warm-up (poly: power 2)")
+    ap.add_argument("--lr-warmup-steps", type=int, default=0,
+                    help="linear learning-rate warm-up steps (--warmup is the timing warm-up)")
+    ap.add_argument("--lr-total-steps", type=int, default=None,
+                    help="step at which the decay reaches --lr-end (default: the job's own step count)")
+    ap.add_argument("--lr-end", type=float, default=0.0, help="learning rate at the end of the decay")
+    ap.add_argument("--label-smoothing", type=float, default=0.0,
+                    help="smoothing of the training loss's targets; evaluation stays the plain cross-entropy")
     return ap
 
 
@@ -545,6 +602,10 @@ def parse_args(argv=None):
         args.steps = 20
     if args.data_workers < 1:
         ap.error("--data-workers >= 1")
+    if not 0.0 <= args.label_smoothing < 1.0:
+        ap.error("--label-smoothing in [0, 1)")
+    if args.lr_warmup_steps < 0:
+        ap.error("--lr-warmup-steps >= 0")
     return args
 
 
