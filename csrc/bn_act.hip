@@ -91,12 +91,6 @@ __host__ __device__ __forceinline__ float* ws_coef(float* ws, int C) {
 // a side stream while the backward finalize of the same BN runs on the main one
 __host__ __device__ __forceinline__ float* ws_bcoef(float* ws, int C) { return ws_coef(ws, C) + 2 * C; }
 
-__device__ __forceinline__ void atomic_add_f32(float* p, float v) {
-  // no-return fp32 atomic (global_atomic_add_f32 with -munsafe-fp-atomics),
-  // executed at the memory side.
-  __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // Block-level fold of per-lane VEC-wide sums over the RPI row groups, then one
 // atomic per channel (and per sum) from the r0 == 0 lanes into the block's replica.
 template <int VEC>

@@ -102,10 +102,30 @@ template <typename T, int VEC> struct VecIO {
   }
 };
 
-__device__ __forceinline__ float wave_sum(float v) {
+// 64-lane butterfly sum of any type __shfl_xor is declared for (float, double,
+// int, unsigned long long, ...): every lane ends with the wave's total.
+template <typename T> __device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
+}
+
+// 64-lane inclusive prefix sum (Hillis-Steele over __shfl_up): lane l ends with
+// the sum of lanes 0..l.
+template <typename T> __device__ __forceinline__ T wave_incl_scan(T v) {
+  const int lane = threadIdx.x & (kWave - 1);
+#pragma unroll
+  for (int o = 1; o < kWave; o <<= 1) {
+    const T u = __shfl_up(v, o, 64);
+    if (lane >= o) v += u;
+  }
+  return v;
+}
+
+// no-return fp32 atomic (global_atomic_add_f32 with -munsafe-fp-atomics),
+// executed at the memory side.
+__device__ __forceinline__ void atomic_add_f32(float* p, float v) {
+  __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // Grid sizing for memory-bound kernels (guide Guideline 11): enough blocks to

@@ -29,25 +29,11 @@
 #include "common.h"
 #include "gemm_epi.h"
 #include "kdl_api.h"
+#include "mfma.h"
 #include "tune.h"
 
 namespace kdl {
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-typedef short v4s_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) v4s_t lds_v4s_t;
-
-// ds_read_b64_tr_b16: per 16-lane group a 4-row x 16-column block, lane i gets
-// column i's 4 rows (device pass only: the host pass has no such builtin)
-__device__ __forceinline__ v4s_t tr_read(const bf16_t* p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s_t*)(p));
-#else
-  return v4s_t{};
-#endif
-}
 
 constexpr int BK = 64;
 constexpr int LDA = BK + 8;  // padded LDS row (bf16 elements)
@@ -876,7 +862,7 @@ __global__ __launch_bounds__(256) void head_bce_fwd_kernel(const bf16_t* __restr
   for (int r = 0; r < R; ++r) {
     float a = acc[r];
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off, 64);
+    for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off, 64);  // (not wave_sum: it compiles to other code here)
     const int m = mb + r;
     if (m < M) {
       const float z = a + bias;
@@ -901,7 +887,7 @@ __global__ __launch_bounds__(256) void head_bce_fwd_kernel(const bf16_t* __restr
   for (int i = threadIdx.x; i < static_cast<int>(gridDim.x); i += 256)
     a += sc1 ? __hip_atomic_load(loss_part + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : loss_part[i];
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off, 64);
+  for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off, 64);  // (not wave_sum: it compiles to other code here)
   if (lane == 0) wave_loss[wv] = a;
   __syncthreads();
   if (threadIdx.x == 0) {

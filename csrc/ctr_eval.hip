@@ -99,12 +99,6 @@ __global__ __launch_bounds__(kAucThreads) void auc_accumulate_kernel(
 constexpr int kFinPerThread = kAucBuckets / kAucThreads;  // 64 buckets per thread
 constexpr int kFinWaves = kAucThreads / kWave;
 
-__device__ __forceinline__ u64 wave_sum_u64(u64 v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += static_cast<u64>(__shfl_xor(static_cast<long long>(v), o, 64));
-  return v;
-}
-
 // unsigned arithmetic throughout: P, N < 2^31 (the caller's precondition) keeps
 // every term and the total below 2 P N < 2^63; past it the sums wrap instead
 // of being undefined
@@ -140,9 +134,9 @@ __global__ __launch_bounds__(kAucThreads) void auc_finalize_kernel(const u64* __
   u64 above = s - p_sum;  // positives in the buckets of higher threads
   for (int w = wave + 1; w < kFinWaves; ++w) above += wtot[w];
   u2 += 2 * above * n_sum;
-  u2 = wave_sum_u64(u2);
-  p_sum = wave_sum_u64(p_sum);
-  n_sum = wave_sum_u64(n_sum);
+  u2 = wave_sum(u2);
+  p_sum = wave_sum(p_sum);
+  n_sum = wave_sum(n_sum);
   if (lane == 0) {
     red[0][wave] = u2;
     red[1][wave] = p_sum;

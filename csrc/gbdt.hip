@@ -92,17 +92,6 @@ __global__ __launch_bounds__(kHistBlock) void hist_build_kernel(
   }
 }
 
-// Wave-level inclusive scan over 64 lanes.
-__device__ __forceinline__ float wave_incl_scan(float v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const float u = __shfl_up(v, o, 64);
-    if (lane >= o) v += u;
-  }
-  return v;
-}
-
 __global__ __launch_bounds__(256) void split_find_kernel(
     const float* __restrict__ hist, int F, int B, float lambda, float min_child_weight,
     float* __restrict__ best_gain, int32_t* __restrict__ best_bin, float* __restrict__ best_gl,
@@ -328,7 +317,7 @@ __global__ __launch_bounds__(kHistBlock) void hist_build_rows_kernel(
         n = sz > 0 ? (sz + rpb - 1) / rpb : 0;
       }
 #pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
+      for (int o = 1; o < 64; o <<= 1) {  // (not wave_incl_scan: it compiles to other code here)
         const int u = __shfl_up(n, o, 64);
         if (t >= o) n += u;
       }
@@ -607,7 +596,7 @@ __global__ __launch_bounds__(256) void route_scan_kernel(
   // block scan of the thread totals
   int x = run;
 #pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
+  for (int o = 1; o < 64; o <<= 1) {  // (not wave_incl_scan: it compiles to other code here)
     const int u = __shfl_up(x, o, 64);
     if (lane >= o) x += u;
   }
@@ -652,7 +641,7 @@ __global__ __launch_bounds__(256) void route_scan_kernel(
         const int stop = pm ? __ffsll(static_cast<long long>(pm)) - 1 : 64;
         int c = lane <= stop ? static_cast<int>(val) : 0;
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+        for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);  // (not wave_sum: it compiles to other code here)
         excl += c;
         if (pm) break;
         j -= 64;
@@ -738,12 +727,7 @@ constexpr int kTilePos = 256 * kRouteItems;  // positions per tile (one block)
 
 __device__ __forceinline__ int block_incl_scan256(int v, int* wsum) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int u = __shfl_up(x, o, 64);
-    if (lane >= o) x += u;
-  }
+  int x = wave_incl_scan(v);
   __syncthreads();  // wsum reuse across calls
   if (lane == 63) wsum[w] = x;
   __syncthreads();
@@ -811,7 +795,7 @@ __global__ __launch_bounds__(1024) void level_plan_kernel(
     const int v = j < ntiles ? tile_cnt[j] : 0;
     int x = v;
 #pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
+    for (int o = 1; o < 64; o <<= 1) {  // (not wave_incl_scan: it compiles to other code here)
       const int u = __shfl_up(x, o, 64);
       if (lane >= o) x += u;
     }

@@ -53,6 +53,7 @@
 // rows fit (F > ~600) the rows stay in global memory (the no-staging variant).
 // Large F therefore runs at 1-2 waves per CU; nothing here is tuned for it.
 #include "common.h"
+#include "gbdt_node.h"
 #include "kdl_api.h"
 
 namespace kdl {
@@ -62,17 +63,6 @@ constexpr int kChunkNodes = 512;
 constexpr int kWalks = 4;  // trees of a chunk walked at once per lane
 constexpr int kChunkBytes = kChunkNodes * static_cast<int>(sizeof(GbdtNode));
 constexpr int kLdsMax = 160 * 1024;
-static_assert(sizeof(GbdtNode) == 16, "GbdtNode is one 16-byte load");
-
-__device__ __forceinline__ GbdtNode load_node(const GbdtNode* p) {
-  const int4 v = *reinterpret_cast<const int4*>(p);
-  GbdtNode n;
-  n.feature = v.x;
-  n.threshold = __int_as_float(v.y);
-  n.left = v.z;
-  n.value = __int_as_float(v.w);
-  return n;
-}
 
 // one row through one tree of ``n`` nodes; false: the table is broken at this walk
 __device__ __forceinline__ bool walk(const GbdtNode* __restrict__ nodes, int n, const float* __restrict__ x, int F,

@@ -241,7 +241,7 @@ __global__ __launch_bounds__(kTile) void rank_ndcg_kernel(const float* __restric
       if (valid && (k <= 0 || pos < k))
         term = static_cast<double>(rank_gain(label[first + i])) * static_cast<double>(dtab[min(pos, dlen - 1)]);
 #pragma unroll
-      for (int o = 32; o > 0; o >>= 1) term += __shfl_xor(term, o, 64);
+      for (int o = 32; o > 0; o >>= 1) term += __shfl_xor(term, o, 64);  // (not wave_sum: it compiles to other code here)
       if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = term;
       __syncthreads();
       if (threadIdx.x == 0) acc += (red[0] + red[1]) + (red[2] + red[3]);

@@ -65,6 +65,7 @@
 // gbdt_contribs_bench.txt): 2M x 28 rows, 100 depth-6 trees (6,304 paths): 71.6 ms, the cover
 // pass over 65,536 rows 0.18 ms; the split between VALU and LDS time has not been measured.
 #include "common.h"
+#include "gbdt_node.h"
 #include "kdl_api.h"
 
 namespace kdl {
@@ -74,7 +75,6 @@ constexpr int kChunkNodes = 512;  // cover pass: GbdtNodes per LDS chunk (predic
 constexpr int kChunkSlots = 512;  // contributions: 16-byte path slots per LDS chunk
 constexpr int kMaxPath = 10;      // merged elements per path (the grower's depth limit)
 constexpr int kLdsMax = 160 * 1024;
-static_assert(sizeof(GbdtNode) == 16, "GbdtNode is one 16-byte load");
 
 // Gauss-Legendre on [0, 1], rules of 1..5 nodes, row Q - 1: node t, 1 - t, weight
 __constant__ float kGlT[5][5] = {
@@ -96,16 +96,6 @@ __constant__ float kGlW[5][5] = {
     {0.1739274225687269f, 0.32607257743127305f, 0.32607257743127305f, 0.1739274225687269f},
     {0.11846344252809454f, 0.23931433524968324f, 0.28444444444444444f, 0.23931433524968324f,
      0.11846344252809454f}};
-
-__device__ __forceinline__ GbdtNode load_node(const GbdtNode* p) {
-  const int4 v = *reinterpret_cast<const int4*>(p);
-  GbdtNode n;
-  n.feature = v.x;
-  n.threshold = __int_as_float(v.y);
-  n.left = v.z;
-  n.value = __int_as_float(v.w);
-  return n;
-}
 
 // stage the block's row tile: coalesced read of cnt * F contiguous floats, row stride ``stride``
 template <int R>

@@ -31,13 +31,11 @@
 
 #include "bn_fin.h"
 #include "common.h"
+#include "mfma.h"
 
 namespace kdl {
 namespace gemm {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 typedef __attribute__((ext_vector_type(2))) float f2_t;
 
 constexpr int kRep = 32;  // replica count of the BN workspace (== bn_act.hip kReplicas)
@@ -165,10 +163,6 @@ __device__ __forceinline__ f2_t pfma(const f2_t a, const f2_t b, const f2_t c) {
 __device__ __forceinline__ uint4 pack8(const float (&o)[8]) {
   return make_uint4(pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3]), pack_bf16x2(o[4], o[5]),
                     pack_bf16x2(o[6], o[7]));
-}
-
-__device__ __forceinline__ void atomic_add_f32(float* p, float v) {
-  __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // D[n][m] of a 32x32x16 MFMA with the weight fragment as the A operand: lane

@@ -38,41 +38,22 @@
 #include "common.h"
 #include "gemm_epi.h"
 #include "kdl_api.h"
+#include "lds_dma.h"
+#include "mfma.h"
 #include "tune.h"
 
 namespace kdl {
 namespace {
 
 using namespace gemm;
+using lds_dma::dma16;
+using lds_dma::i32x4_t;
+using lds_dma::kOOB;
+using lds_dma::lds_void_t;
+using lds_dma::rsrc_words;
 
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((ext_vector_type(4))) int i32x4_t;
-
-constexpr uint32_t kOOB = 0x80000000u;  // voffset past every buffer: zeros
 constexpr int kWaves = 7, kNT = 64 * kWaves, kBM = 32 * kWaves;  // 224-pixel tiles
 constexpr int kBRows = 576;            // resident weight rows: 9 taps x Cin/64 chunks x BN
-
-__device__ __forceinline__ i32x4_t rsrc_words(const void* base, uint32_t bytes) {
-  const uint64_t a = reinterpret_cast<uint64_t>(base);
-  i32x4_t r;
-  r.x = __builtin_amdgcn_readfirstlane(static_cast<int>(a & 0xffffffffu));
-  r.y = __builtin_amdgcn_readfirstlane(static_cast<int>((a >> 32) & 0xffffu));
-  r.z = __builtin_amdgcn_readfirstlane(static_cast<int>(bytes));
-  r.w = 0x00020000;
-  return r;
-}
-
-// 16 B per lane LDS-DMA (1 KiB per wave instruction at dst + 16 * lane), from
-// inline asm: the compiler sees no LDS write, so it adds no waits of its own.
-__device__ __forceinline__ void dma16(i32x4_t r, lds_void_t* dst, uint32_t voff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  const uint32_t m0 = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(reinterpret_cast<uintptr_t>(dst)));
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds"
-               :
-               : "s"(m0), "v"(voff), "s"(r)
-               : "memory", "m0");
-#endif
-}
 
 // PRO: the previous layer's BN + ReLU, relu(x * scale + shift) with
 // p.pro_coef = [scale | shift] per input channel, applied to the halo in LDS
@@ -353,22 +334,6 @@ constexpr int kWgStage = (kWgDyRows + kWgHRows) * 128;  // 73,728 B
 constexpr int kWgIPW = (kWgDyRows + kWgHRows) / 8 / kWgWaves;
 static_assert((kWgDyRows + kWgHRows) % (8 * kWgWaves) == 0, "every wave issues the same DMA count");
 static_assert(4 * 9 * 16 * 64 * 4 <= 2 * kWgStage, "K-parity combine fits the stage buffers");
-
-typedef short v4s_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) v4s_t lds_v4s_t;
-
-__device__ __forceinline__ v4s_t tr_read(const char* p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s_t*)(p));
-#else
-  return v4s_t{};
-#endif
-}
-
-__device__ __forceinline__ bf16x8_t frag8(v4s_t lo, v4s_t hi) {
-  const uint2 a = __builtin_bit_cast(uint2, lo), b = __builtin_bit_cast(uint2, hi);
-  return __builtin_bit_cast(bf16x8_t, make_uint4(a.x, a.y, b.x, b.y));
-}
 
 __device__ __forceinline__ int trswz(int R) { return ((R >> 1) & 1) * 4; }
 

@@ -26,12 +26,10 @@
 // summed in a fixed order by the consumer (deterministic, no atomics).
 #include "common.h"
 #include "kdl_api.h"
+#include "mfma.h"
 
 namespace kdl {
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
 
 constexpr int kT = 64;       // output tile (rows and columns)
 constexpr int kBK = 64;      // K per stage

@@ -54,7 +54,6 @@ using namespace gemm;
 
 using lds_dma::lds_void_t;
 using lds_dma::i32x4_t;
-using lds_dma::kOOB;
 using lds_dma::rsrc_words;
 using lds_dma::dma16;
 using lds_dma::publish_stage;

@@ -1,11 +1,12 @@
-// LDS-DMA helpers shared by the LDS-DMA GEMM main loops (csrc/igemm.hip,
-// csrc/wgrad_dma.hip): raw buffer-resource words and one 16-byte-per-lane
-// `buffer_load_dwordx4 ... lds` (1 KiB per wave at M0 + 16 * lane) issued from
-// inline asm.  The asm form matters twice: hipcc does not see an LDS write, so
-// it inserts no vmcnt wait of its own before the fragment reads of the stage
-// being multiplied (the caller's counted s_waitcnt + barrier are the only
-// ordering); and M0 is written in the same statement as the load, so no
-// compiler-placed spill or M0 use can land between them.
+// LDS-DMA helpers shared by every kernel that stages operands by LDS-DMA
+// (csrc/igemm.hip, csrc/wgrad_dma.hip, csrc/halo3x3.hip, csrc/stem.hip): raw
+// buffer-resource words and one 16-byte-per-lane `buffer_load_dwordx4 ... lds`
+// (1 KiB per wave at M0 + 16 * lane) issued from inline asm.  The asm form
+// matters twice: hipcc does not see an LDS write, so it inserts no vmcnt wait of
+// its own before the fragment reads of the stage being multiplied (the caller's
+// counted s_waitcnt + barrier are the only ordering); and M0 is written in the
+// same statement as the load, so no compiler-placed spill or M0 use can land
+// between them.
 #pragma once
 
 #include <cstdint>
@@ -39,6 +40,30 @@ __device__ __forceinline__ void dma16(i32x4_t r, lds_void_t* dst, uint32_t voff,
                :
                : "s"(m0), "v"(voff), "s"(r), "s"(soff)
                : "memory", "m0");
+#endif
+}
+
+// no scalar offset: the immediate 0 (a constant through the "s" operand above
+// would cost an SGPR move)
+__device__ __forceinline__ void dma16(i32x4_t r, lds_void_t* dst, uint32_t voff) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const uint32_t m0 = __builtin_amdgcn_readfirstlane(
+      static_cast<uint32_t>(reinterpret_cast<uintptr_t>(dst)));
+  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds"
+               :
+               : "s"(m0), "v"(voff), "s"(r)
+               : "memory", "m0");
+#endif
+}
+
+// The same 16-byte LDS-DMA through the compiler's builtin, on a resource from
+// __builtin_amdgcn_make_buffer_rsrc.  Here the compiler sees the LDS write and
+// places the waits itself: right for a loop synchronised by plain
+// __syncthreads(); the asm forms above are for loops that keep loads in flight
+// across barriers under their own counted waits.
+__device__ __forceinline__ void dma16_builtin(__amdgpu_buffer_rsrc_t r, lds_void_t* dst, uint32_t voff) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, dst, 16, voff, 0, 0, 0);
 #endif
 }
 

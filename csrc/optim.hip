@@ -176,12 +176,6 @@ PLAIN_F32_KERNEL __global__ __launch_bounds__(256) void lars_norms_kernel(
         ((sh[threadIdx.x][0] + sh[threadIdx.x][1]) + sh[threadIdx.x][2]) + sh[threadIdx.x][3];
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 template <typename GT, typename PT>
 PLAIN_F32_KERNEL __global__ __launch_bounds__(256) void lars_update_kernel(
     const OptChunk* __restrict__ chunks, const LarsChunk* __restrict__ meta, int nchunks,
@@ -199,8 +193,8 @@ PLAIN_F32_KERNEL __global__ __launch_bounds__(256) void lars_update_kernel(
         sg += static_cast<double>(part[m.first + i]);
         sw += static_cast<double>(part[static_cast<int64_t>(nchunks) + m.first + i]);
       }
-      sg = wave_sum_f64(sg);
-      sw = wave_sum_f64(sw);
+      sg = wave_sum(sg);
+      sw = wave_sum(sw);
       if (sg > 0.0 && sw > 0.0) {
         const double gn = fabs(static_cast<double>(h.grad_scale)) * sqrt(sg), wn = sqrt(sw);
         t = static_cast<float>(static_cast<double>(h.eta) * wn /

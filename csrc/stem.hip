@@ -25,6 +25,8 @@
 #include "common.h"
 #include "gemm_epi.h"
 #include "kdl_api.h"
+#include "lds_dma.h"
+#include "mfma.h"
 
 namespace kdl {
 namespace {
@@ -245,29 +247,11 @@ int g_stem_drop = 0;
 // patch matrix is ever built.  Wave w owns kernel row r = w (32 k) for both
 // 32-channel halves; the block's fp32 partial goes to its own slab, summed in
 // a fixed order by wgrad_slab_reduce (deterministic).
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef short v4s_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) v4s_t lds_v4s_t;
-constexpr uint32_t kOOB = 0x80000000u;
-
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, lds_void_t* dst, uint32_t voff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, dst, 16, voff, 0, 0, 0);
-#endif
-}
-
-__device__ __forceinline__ v4s_t tr_read(const char* p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s_t*)(p));
-#else
-  return v4s_t{};
-#endif
-}
-
-__device__ __forceinline__ bf16x8_t frag8(v4s_t lo, v4s_t hi) {
-  const uint2 a = __builtin_bit_cast(uint2, lo), b = __builtin_bit_cast(uint2, hi);
-  return __builtin_bit_cast(bf16x8_t, make_uint4(a.x, a.y, b.x, b.y));
-}
+// The DMA goes through the compiler's builtin (lds_dma::dma16_builtin): the
+// loop below synchronises with plain __syncthreads().
+using lds_dma::dma16_builtin;
+using lds_dma::kOOB;
+using lds_dma::lds_void_t;
 
 // FUSE: dY is not in memory -- each tile's 224 x 64 gradient rows are built
 // in LDS from the stem conv output c0, the pooled gradient and its argmax
@@ -325,7 +309,7 @@ __global__ __launch_bounds__(kNT, 4) void stem_wgrad_kernel(const bf16_t* __rest
       } else {
         voff = static_cast<uint32_t>((static_cast<int64_t>(tm) * kBM + r) * 128 + 16 * c);
       }
-      dma16(rG, (lds_void_t*)(Gs + buf * G_BYTES + g * 1024), voff);
+      dma16_builtin(rG, (lds_void_t*)(Gs + buf * G_BYTES + g * 1024), voff);
     }
   };
 
@@ -357,9 +341,9 @@ __global__ __launch_bounds__(kNT, 4) void stem_wgrad_kernel(const bf16_t* __rest
     for (int i = 0; i < 3; ++i) {
       const int g = wave * 3 + i;  // 0..20
       if (g < DP_BYTES / 1024)
-        dma16(rD, (lds_void_t*)(Ps + g * 1024), cell0 * 128 + g * 1024 + 16 * lane);
+        dma16_builtin(rD, (lds_void_t*)(Ps + g * 1024), cell0 * 128 + g * 1024 + 16 * lane);
       else
-        dma16(rI, (lds_void_t*)(Ps + DP_BYTES + (g - DP_BYTES / 1024) * 1024),
+        dma16_builtin(rI, (lds_void_t*)(Ps + DP_BYTES + (g - DP_BYTES / 1024) * 1024),
               cell0 * 64 + (g - DP_BYTES / 1024) * 1024 + 16 * lane);
     }
   };

@@ -31,6 +31,7 @@
 #include "gemm_epi.h"
 #include "kdl_api.h"
 #include "lds_dma.h"
+#include "mfma.h"
 
 #include <type_traits>
 
@@ -44,25 +45,8 @@ using lds_dma::kOOB;
 using lds_dma::lds_void_t;
 using lds_dma::publish_stage;
 using lds_dma::rsrc_words;
-typedef short v4s_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) v4s_t lds_v4s_t;
 
 constexpr int MK = 64;  // rows (m) per stage
-
-// (device-pass guard: referenced in the host pass this builtin makes clang
-// drop the kernel's host stub)
-__device__ __forceinline__ v4s_t tr_read(const char* p) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s_t*)(p));
-#else
-  return v4s_t{};
-#endif
-}
-
-__device__ __forceinline__ bf16x8_t frag8(v4s_t lo, v4s_t hi) {
-  const uint2 a = __builtin_bit_cast(uint2, lo), b = __builtin_bit_cast(uint2, hi);
-  return __builtin_bit_cast(bf16x8_t, make_uint4(a.x, a.y, b.x, b.y));
-}
 
 // WN x WK waves: 2 x 2 (4 waves, 2 blocks/CU) for tiles up to 128 x 128; 2 x 4
 // (8 waves of 128 x 64, 1 block/CU, 128 KiB) for 256 x 256 -- half the LDS-DMA
