@@ -673,7 +673,45 @@ void gbdt_contribs(const at::Tensor& X, const at::Tensor& paths, const at::Tenso
             "gbdt_contribs");
 }
 
-// g, h fp32 [N, 1] of rank:pairwise / rank:ndcg (csrc/gbdt_rank.hip).  plan_wave / plan_block int32 [*, 4]: the
+// out [N, K, F + 1, F + 1] = the per-feature path table's SHAP interaction values of X's rows, bias[k] at
+// [F, F] (csrc/gbdt_interactions.hip).  paths int32 [slots, 4]; chunk_off int32 [chunks + 1]; feat_chunk
+// int32 [K * F + 1]
+void gbdt_interactions(const at::Tensor& X, const at::Tensor& paths, const at::Tensor& chunk_off,
+                       const at::Tensor& feat_chunk, const at::Tensor& bias, int64_t K, const at::Tensor& out) {
+  TORCH_CHECK(X.is_cuda() && X.scalar_type() == at::kFloat && X.dim() == 2 && X.is_contiguous() && X.size(1) >= 1,
+              "gbdt_interactions: X must be a contiguous fp32 [N, F] GPU tensor");
+  TORCH_CHECK(X.size(1) < 65535, "gbdt_interactions: fewer than 65535 features (F + 1 is a grid dimension)");
+  TORCH_CHECK(1 <= K && K <= 32, "gbdt_interactions: 1 <= K <= 32");
+  TORCH_CHECK(paths.is_cuda() && paths.scalar_type() == at::kInt && paths.dim() == 2 && paths.size(1) == 4 &&
+                  paths.is_contiguous() && paths.numel() < (int64_t{1} << 31),
+              "gbdt_interactions: paths must be a contiguous int32 [slots, 4] GPU tensor");
+  TORCH_CHECK(chunk_off.is_cuda() && chunk_off.scalar_type() == at::kInt && chunk_off.dim() == 1 &&
+                  chunk_off.is_contiguous() && chunk_off.numel() >= 1,
+              "gbdt_interactions: chunk_off must be a contiguous int32 [chunks + 1] GPU tensor");
+  TORCH_CHECK(feat_chunk.is_cuda() && feat_chunk.scalar_type() == at::kInt && feat_chunk.dim() == 1 &&
+                  feat_chunk.is_contiguous() && feat_chunk.numel() == K * X.size(1) + 1,
+              "gbdt_interactions: feat_chunk must be a contiguous int32 [K * F + 1] GPU tensor");
+  TORCH_CHECK(bias.is_cuda() && bias.scalar_type() == at::kFloat && bias.dim() == 1 && bias.is_contiguous() &&
+                  bias.numel() == K,
+              "gbdt_interactions: bias must be a contiguous fp32 [K] GPU tensor");
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kFloat && out.dim() == 4 && out.is_contiguous() &&
+                  out.size(0) == X.size(0) && out.size(1) == K && out.size(2) == X.size(1) + 1 &&
+                  out.size(3) == X.size(1) + 1,
+              "gbdt_interactions: out must be a contiguous fp32 [N, K, F + 1, F + 1] GPU tensor");
+  TORCH_CHECK(paths.device() == X.device() && chunk_off.device() == X.device() &&
+                  feat_chunk.device() == X.device() && bias.device() == X.device() && out.device() == X.device(),
+              "gbdt_interactions: tensors on different devices");
+  if (X.size(0) == 0) return;
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(X.device());
+  check_hip(kdl::gbdt_interactions(X.data_ptr<float>(), X.size(0), static_cast<int>(X.size(1)),
+                                   paths.data_ptr<int32_t>(), static_cast<int>(paths.size(0)),
+                                   chunk_off.data_ptr<int32_t>(), static_cast<int>(chunk_off.numel() - 1),
+                                   feat_chunk.data_ptr<int32_t>(), bias.data_ptr<float>(), static_cast<int>(K),
+                                   out.data_ptr<float>(), cur_stream()),
+            "gbdt_interactions");
+}
+
+// g, h fp32 [N, 1] of rank:pairwise / rank:ndcg (csrc/gbdt_rank.hip). plan_wave / plan_block int32 [*, 4]: the
 // host-built work plan; dtab fp32 [L]: the discount table, L >= max_group; disc fp32 [N]: workspace
 std::vector<at::Tensor> gbdt_rank_grad_hess(const at::Tensor& score, const at::Tensor& label,
                                             const at::Tensor& plan_wave, const at::Tensor& plan_block,
@@ -2272,6 +2310,11 @@ PYBIND11_MODULE(_C, m) {
   m.def("gbdt_heap_nodes", &gbdt_heap_nodes, "the grower's [4, heap] arrays -> packed forest nodes, on the device");
   m.def("gbdt_cover", &gbdt_cover, "cover pass: counts[node] += rows of X reaching the node, trees [t0, t1)");
   m.def("gbdt_contribs", &gbdt_contribs, "exact TreeSHAP of a path table: out[N, K, F + 1]");
+  m.def("gbdt_interactions", &gbdt_interactions, "SHAP interaction values of a per-feature path table: out[N, K, F + 1, F + 1]");
+  m.def("gbdt_interactions_chunk_slots", &kdl::gbdt_interactions_chunk_slots,
+        "16-byte path slots per LDS chunk of the interaction kernel (whole paths)");
+  m.def("gbdt_interactions_rows_per_block", &kdl::gbdt_interactions_rows_per_block,
+        "rows per block of the interaction kernel for F features (0: nothing staged in LDS)");
   m.def("gbdt_rank_grad_hess", &gbdt_rank_grad_hess, "rank:pairwise / rank:ndcg g, h [N, 1] over a host-built plan");
   m.def("gbdt_rank_ndcg", &gbdt_rank_ndcg, "per group DCG@k in fp64 [Q] (k <= 0: the whole list)");
   m.def("gbdt_rank_wave_max", &kdl::gbdt_rank_wave_max, "largest group of the one-wave path");

@@ -293,6 +293,17 @@ hipError_t gbdt_contribs(const float* X, int64_t N, int F, const int32_t* paths,
 int gbdt_contribs_chunk_slots();          // 16-byte path slots per LDS chunk (whole paths)
 int gbdt_contribs_rows_per_block(int F);  // 256 / 128 / 64, or 0: rows and accumulators not in LDS
 
+// ---- gbdt_interactions.hip (SHAP interaction values: HistGBDT.predict_interactions)
+// out [N, K, F + 1, F + 1] = the Shapley interaction index of every feature pair, the diagonal so that
+// the last axis sums to gbdt_contribs' result, bias[k] at [F, F] (formula and per-feature table layout:
+// the file's header; paths int32 [num_slots, 4], chunk_off int32 [num_chunks + 1], feat_chunk int32
+// [K * F + 1]).  Every element is written; no atomics; 1 <= K <= 32, F < 65535
+hipError_t gbdt_interactions(const float* X, int64_t N, int F, const int32_t* paths, int num_slots,
+                             const int32_t* chunk_off, int num_chunks, const int32_t* feat_chunk, const float* bias,
+                             int K, float* out, hipStream_t s);
+int gbdt_interactions_chunk_slots();          // 16-byte path slots per LDS chunk (whole paths)
+int gbdt_interactions_rows_per_block(int F);  // 256 / 128 / 64, or 0: rows and accumulators not in LDS
+
 // ---- gbdt_rank.hip (learning to rank: the LambdaMART pair kernels and the DCG of ndcg@k)
 // g, h [N] of rank:pairwise (ndcg = false) or rank:ndcg over a host-built plan (layout: gbdt_rank.hip's header):
 // plan_wave int32 [wave_slots, 4] (groups of <= gbdt_rank_wave_max() rows), plan_block int32 [block_items, 4]

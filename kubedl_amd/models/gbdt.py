@@ -43,6 +43,29 @@ TreeSHAP values [N, K, F + 1] (csrc/gbdt_shap.hip: the cover kernel and the
 contribution kernel over a host-built table of root-to-leaf paths; on CPU the
 same path formula on torch ops in fp64).
 
+Interaction values: ``predict_interactions`` returns fp32 [N, K, F + 1, F + 1] in
+XGBoost's ``pred_interactions`` layout (csrc/gbdt_interactions.hip over a
+per-feature table of the same paths; on CPU ``_interactions_torch``, fp64 rounded
+once).  The definition, shared by both paths and by the tests, in the notation of
+csrc/gbdt_shap.hip (a path of class k: leaf value v, m <= 10 merged elements with
+feature f_l, zero fraction z_l and o_l in {0, 1} the interval test on the row):
+
+* ``i != j``, both ``< F``: ``Phi[n, k, i, j]`` is the sum, over the paths of class k
+  that hold both features, of ``0.5 * v * (o_i - z_i) * (o_j - z_j) * W_ij`` with
+  ``W_ij = int_0^1 prod_{l != i, j} (o_l t + z_l (1 - t)) dt`` -- the Shapley
+  interaction index of ``S -> E_t(x, S)``; ``s! (m - 2 - s)! / (m - 1)!`` is the Beta
+  integral of ``t^s (1 - t)^(m - 2 - s)``.  ``W_ij = 1`` for ``m = 2``; a path with
+  ``m = 1`` has no off-diagonal term.
+* Diagonal: ``Phi[n, k, i, i] = phi_i - sum_{j != i} Phi[n, k, i, j]`` with ``phi_i``
+  the contribution of ``predict_contribs``, per path ``v (o_i - z_i) W_i``.
+* Bias: ``Phi[n, k, F, F] = bias[k]`` (the fp64-summed bias of ``predict_contribs``,
+  paths with ``m = 0`` included); the rest of row ``F`` and column ``F`` is 0.
+* So the matrix is symmetric up to rounding, its last axis sums to
+  ``predict_contribs`` and both axes sum to the raw margin.
+
+Every integrand has degree at most ``m - 1``: Gauss-Legendre with ``ceil(m / 2)``
+nodes is exact for ``W_i`` and ``W_ij``.
+
 Learning to rank: objectives ``rank:pairwise`` and ``rank:ndcg`` (LambdaMART).  On the
 GPU the gradient is the pair kernels of csrc/gbdt_rank.hip over a work plan built
 once per ``fit``; on CPU the same definition on torch ops in fp64, rounded once.  The
@@ -174,6 +197,7 @@ class HistGBDT:
         self._forest_cache = None  # (key, trees kept alive, nodes, tree_off, max feature): _forest()
         self._cover_cache = None  # (forest key, int64 covers [num_nodes], background F): set_background()
         self._paths_cache = None  # (key, path table): _path_table()
+        self._pairs_cache = None  # (the same key, per-feature path table): _pair_table()
 
     # ------------------------------------------------------------ quantisation
     def fit_cuts(self, X: torch.Tensor, sample: int = 65536, seed: int = 0) -> None:
@@ -972,7 +996,7 @@ class HistGBDT:
             self._cover_torch(X, nodes, off, counts)
         _allreduce_(counts)
         self._cover_cache = (self._forest_cache[0], counts, X.shape[1])
-        self._paths_cache = None
+        self._paths_cache = self._pairs_cache = None
         return counts
 
     @staticmethod
@@ -1170,6 +1194,145 @@ class HistGBDT:
                                       out.shape[1], out)
             return out
         return self._contribs_torch(X, table)
+
+    # ------------------------------------------------------------ interaction values
+    def _pair_table(self, n_rounds: int, F: int) -> dict:
+        """``_path_table``'s paths regrouped for csrc/gbdt_interactions.hip (its header
+        has the layout): per class and per feature a path of the class splits on, the
+        paths that hold the feature, in table order, with that feature's element
+        rotated to slot 0; the same 16-byte slots.  Every (class, feature) list is cut
+        into chunks of whole paths; list ``k * F + i`` owns chunks
+        ``[feat_chunk[k * F + i], feat_chunk[k * F + i + 1])``.  Cached beside the path
+        table, under its key."""
+        import numpy as np
+        table = self._path_table(n_rounds)
+        key = (self._paths_cache[0], F)
+        if self._pairs_cache is not None and self._pairs_cache[0] == key:
+            return self._pairs_cache[1]
+        pad, K = table["pad"], self._num_class()
+        m = pad["valid"].sum(1)
+        pp, ee = np.nonzero(pad["valid"])  # one copy of path pp per element ee (a path's elements are its first m)
+        gid = pad["cls"][pp] * F + pad["feat"][pp, ee]
+        order = np.lexsort((pp, gid))  # by list, then table order
+        pp, ee, gid = pp[order], ee[order], gid[order]
+        mg = m[pp]
+        start = np.concatenate([[0], np.cumsum(1 + mg + (mg + 3) // 4)]).astype(np.int64)
+        if start[-1] >= 2 ** 29:  # sum m^2 slots, not sum m: the int32 table's limit comes sooner here
+            raise ValueError("predict_interactions: per-feature path table of 2^29 or more slots")
+        limit = _ext.load().gbdt_interactions_chunk_slots() if self.use_hip else 512
+        chunk_off, feat_chunk, cur = [0], [0] * (K * F + 1), 0
+        for g in range(len(pp)):
+            if gid[g] != cur or start[g + 1] - chunk_off[-1] > limit:
+                if start[g] > chunk_off[-1]:
+                    chunk_off.append(int(start[g]))
+                for kk in range(cur + 1, int(gid[g]) + 1):
+                    feat_chunk[kk] = len(chunk_off) - 1
+                cur = int(gid[g])
+        if start[-1] > chunk_off[-1]:
+            chunk_off.append(int(start[-1]))
+        for kk in range(cur + 1, K * F + 1):
+            feat_chunk[kk] = len(chunk_off) - 1
+        # slot s of copy g: the rotated element first, then the others in their order
+        eg = np.repeat(np.arange(len(pp)), mg)
+        s = np.arange(len(eg)) - np.repeat(np.cumsum(mg) - mg, mg)
+        src = np.where(s == 0, ee[eg], np.where(s <= ee[eg], s - 1, s))
+        sp, head = pp[eg], start[:-1]
+        slots = np.zeros((int(start[-1]), 4), dtype=np.int32)
+        fl = slots.view(np.float32)
+        fl[head, 0] = pad["v"][pp]
+        slots[head, 1] = mg
+        at = head[eg] + 1 + s
+        slots[at, 0] = pad["feat"][sp, src] | (pad["hl"][sp, src].astype(np.int64) << 30)
+        fl[at, 1], fl[at, 2], fl[at, 3] = pad["lo"][sp, src], pad["hi"][sp, src], pad["z"][sp, src]
+        fl[head[eg] + 1 + mg[eg] + s // 4, s % 4] = 1.0 - pad["z"][sp, src]  # rounded from fp64
+        dev = self.device
+        pairs = {"slots": torch.from_numpy(slots).to(dev),
+                 "chunk_off": torch.tensor(chunk_off, dtype=torch.int32, device=dev),
+                 "feat_chunk": torch.tensor(feat_chunk, dtype=torch.int32, device=dev)}
+        self._pairs_cache = (key, pairs)
+        return pairs
+
+    def _interactions_torch(self, X: torch.Tensor, table: dict) -> torch.Tensor:
+        """``predict_interactions`` on torch ops, fp64 inside and rounded once at the end:
+        the module docstring's formula over ``_path_table``'s padded paths.  For each
+        conditioning slot ``a`` the factor of ``a`` is set to 1, so prefix times suffix
+        products give ``W_ab`` at ``b != a`` and ``W_a`` at ``b = a``.  The CPU path."""
+        import numpy as np
+        N, F = X.shape
+        K, F1, dev = self._num_class(), F + 1, X.device
+        pad = {k: torch.from_numpy(v).to(dev) for k, v in table["pad"].items()}
+        P, M = pad["feat"].shape
+        out = torch.zeros(N, K, F1, F1, dtype=torch.float32, device=dev)
+        if N == 0:
+            return out
+        Q = max((M + 1) // 2, 1)  # exact for degree M - 1
+        gx, gw = np.polynomial.legendre.leggauss(Q)
+        tq = torch.from_numpy((gx + 1) / 2).to(dev)
+        wq = torch.from_numpy(gw / 2).to(dev)
+        bias = torch.tensor(table["bias64"], dtype=torch.float64, device=dev)
+        nr = max(1, min(N, (1 << 24) // (K * F1 * F1)))
+        pc = max(1, (1 << 22) // (nr * max(M, 1) * Q))
+        for r0 in range(0, N, nr):
+            Xr = X[r0:r0 + nr].double()
+            n = Xr.shape[0]
+            phi = torch.zeros(n, K * F1 * F1, dtype=torch.float64, device=dev)
+            for p0 in range(0, P, pc):
+                s = slice(p0, p0 + pc)
+                f, z, valid = pad["feat"][s], pad["z"][s], pad["valid"][s]
+                xv = Xr[:, f.reshape(-1)].view(n, -1, M)
+                o = (~(xv <= pad["lo"][s]) & (~pad["hl"][s] | (xv <= pad["hi"][s]))) | ~valid
+                fac = o.double()[..., None] * tq + (z[..., None] * (1 - tq))
+                fac = torch.where(valid[..., None], fac, torch.ones_like(fac))
+                ones = torch.ones(n, fac.shape[1], 1, Q, dtype=torch.float64, device=dev)
+                d = torch.where(o, 1.0 - z, -z) * valid  # o - z, 0 at the padding
+                v = pad["v"][s][None, :, None]
+                cell = pad["cls"][s][:, None] * (F1 * F1) + f  # + f_a * F1: the entry's flat index
+                for a in range(M):
+                    fa = fac.clone()
+                    fa[:, :, a] = 1.0
+                    pre = torch.cat([ones, fa[:, :, :-1]], 2).cumprod(2)
+                    suf = torch.cat([fa[:, :, 1:], ones], 2).flip(2).cumprod(2).flip(2)
+                    W = (pre * suf * wq).sum(-1)
+                    term = 0.5 * v * d[:, :, a:a + 1] * d * W
+                    term[:, :, a] = 0.0
+                    term[:, :, a] = v[..., 0] * d[:, :, a] * W[:, :, a] - term.sum(-1)
+                    phi.index_add_(1, (cell + f[:, a:a + 1] * F1).reshape(-1), term.reshape(n, -1))
+            phi = phi.view(n, K, F1, F1)
+            phi[:, :, F, F] = bias
+            out[r0:r0 + n] = phi.float()
+        return out
+
+    def predict_interactions(self, X: torch.Tensor, n_rounds: Optional[int] = None) -> torch.Tensor:
+        """SHAP interaction values of the raw margin, fp32 [N, K, F + 1, F + 1] in XGBoost's
+        ``pred_interactions`` layout (the module docstring has the definition): the
+        Shapley interaction index off the diagonal, the diagonal so that the last axis
+        sums to ``predict_contribs(X)``, the bias at ``[F, F]``.  Needs the covers of
+        ``set_background``; ``n_rounds`` as in ``predict``.  On the GPU this is the kernel
+        of csrc/gbdt_interactions.hip, on CPU ``_interactions_torch``.  The result holds
+        ``N K (F + 1)^2`` floats: call it on row blocks of a large ``X``."""
+        if X.dim() != 2:
+            raise ValueError(f"predict_interactions: X must be [N, F], got {tuple(X.shape)}")
+        if self.cuts is not None and X.shape[1] != self.cuts.shape[0]:
+            raise ValueError(f"predict_interactions: X has {X.shape[1]} features, the model was fitted on "
+                             f"{self.cuts.shape[0]}")
+        total = len(self.trees)
+        if n_rounds is None:
+            n_rounds = total if self.best_iteration is None else self.best_iteration + 1
+        if not 0 <= n_rounds <= total:
+            raise ValueError(f"predict_interactions: n_rounds {n_rounds} outside the model's {total} rounds")
+        table = self._path_table(n_rounds)
+        if X.shape[1] != self._cover_cache[2]:
+            raise ValueError(f"predict_interactions: X has {X.shape[1]} features, the background set had "
+                             f"{self._cover_cache[2]}")
+        X = X.to(self.device).float().contiguous()
+        if self.use_hip and X.is_cuda:
+            N, F, K = X.shape[0], X.shape[1], self._num_class()
+            pairs = self._pair_table(n_rounds, F)
+            out = torch.empty(N, K, F + 1, F + 1, dtype=torch.float32, device=self.device)
+            _ext.load().gbdt_interactions(X, pairs["slots"], pairs["chunk_off"], pairs["feat_chunk"], table["bias"],
+                                          K, out)
+            return out
+        return self._interactions_torch(X, table)
 
     # ------------------------------------------------------------ model file
     FORMAT_VERSION = 1

@@ -38,7 +38,12 @@ also writes the per-feature contributions [rows, K, F + 1] of
 ``HistGBDT.predict_contribs`` to ``<model file>.contribs.rank<R>.npy`` (the
 background set is every rank's shard, the covers all-reduced) and adds
 ``contribs_seconds`` and the largest ``|sum of contributions - margin|`` to the
-JSON line.  A missing model file is an
+JSON line.  With ``--pred_interactions`` it writes the SHAP interaction values
+[rows, K, F + 1, F + 1] of ``HistGBDT.predict_interactions`` to
+``<model file>.interactions.rank<R>.npy``, computed ``--interactions_block_rows`` rows
+at a time (default: blocks of at most 256 MiB) straight into the memory-mapped file,
+so neither the device nor the host holds the whole result, and adds
+``interactions_seconds`` and the largest ``|sum over both axes - margin|``.  A missing model file is an
 error (exit code 2), never a retrain.  ``examples/xgboost/`` has a Train and a
 Predict job spec that share a model path.
 """
@@ -163,6 +168,26 @@ def run_predict(args, info) -> int:
         np.save(contribs_path, phi.cpu().numpy())
         extra = {"contribs_seconds": cdt, "contribs_max_abs_sum_minus_margin": kdist.all_reduce_max(gap, info),
                  "contribs": contribs_path}
+    if args.pred_interactions:
+        if not args.pred_contribs:
+            model.set_background(X)
+        N, F1, K = int(X.shape[0]), int(X.shape[1]) + 1, int(margin.shape[1])
+        step = args.interactions_block_rows or max((1 << 26) // (K * F1 * F1), 1)
+        inter_path = f"{path}.interactions.rank{info.rank}.npy"
+        dst = np.lib.format.open_memmap(inter_path, mode="w+", dtype=np.float32, shape=(N, K, F1, F1))
+        model.predict_interactions(X[:min(N, step)])  # code loading + per-feature path table
+        sync()
+        gap, t0 = 0.0, time.perf_counter()
+        for r0 in range(0, N, step):
+            blk = model.predict_interactions(X[r0:r0 + step])
+            gap = max(gap, float((blk.double().sum((-1, -2)) - margin[r0:r0 + step].double()).abs().max()))
+            dst[r0:r0 + step] = blk.cpu().numpy()
+        sync()
+        idt = kdist.all_reduce_max(time.perf_counter() - t0, info)
+        dst.flush()
+        del dst
+        extra.update({"interactions_seconds": idt, "interactions": inter_path, "interactions_block_rows": step,
+                      "interactions_max_abs_sum_minus_margin": kdist.all_reduce_max(gap, info)})
     if info.rank == 0:
         print(json.dumps({"job_type": "Predict", "rank": info.rank, "world_size": info.world_size,
                           "objective": model.p.objective, "rounds": len(model.trees), "rows": int(X.shape[0]),
@@ -194,6 +219,8 @@ def main(argv=None) -> int:
     ap.add_argument("--eval_fraction", type=float, default=0.0)
     ap.add_argument("--early_stopping_rounds", type=int, default=0)
     ap.add_argument("--pred_contribs", action="store_true")
+    ap.add_argument("--pred_interactions", action="store_true")
+    ap.add_argument("--interactions_block_rows", type=int, default=0)
     args, _unknown = ap.parse_known_args(argv)
     if os.environ.get("KDL_RANK"):
         os.environ["RANK"] = os.environ["KDL_RANK"]
