@@ -1213,6 +1213,54 @@ void augment_batch(const at::Tensor& images, const at::Tensor& labels, const at:
             "augment_batch");
 }
 
+// the pair-mix launch (Mixup / CutMix): image b mixed with image B-1-b, labels of both
+void augment_mix_batch(const at::Tensor& images, const at::Tensor& labels, const at::Tensor& plan, int64_t row0,
+                       int64_t B, int64_t OH, int64_t OW, const std::vector<double>& A,
+                       const std::vector<double>& Bc, int64_t kind, int64_t lam16, const std::vector<int64_t>& box,
+                       at::Tensor x, at::Tensor y_a, at::Tensor y_b) {
+  TORCH_CHECK(images.is_cuda() && images.scalar_type() == at::kByte && images.dim() == 4 && images.size(3) == 3 &&
+                  images.is_contiguous() && images.size(0) >= 1,
+              "augment_mix_batch: images u8 [n, H, W, 3] contiguous");
+  const int64_t n = images.size(0), H = images.size(1), W = images.size(2);
+  TORCH_CHECK(H >= 1 && W >= 1 && H <= 65536 && W <= 65536, "augment_mix_batch: stored H, W in [1, 65536]");
+  TORCH_CHECK(labels.is_cuda() && labels.scalar_type() == at::kLong && labels.dim() == 1 && labels.is_contiguous() &&
+                  labels.numel() == n,
+              "augment_mix_batch: labels int64 [n] contiguous");
+  TORCH_CHECK(plan.is_cuda() && plan.scalar_type() == at::kInt && plan.dim() == 2 && plan.size(1) == 8 &&
+                  plan.is_contiguous(),
+              "augment_mix_batch: plan int32 [rows, 8] contiguous");
+  TORCH_CHECK(B >= 1 && row0 >= 0 && row0 + B <= plan.size(0) && B < (int64_t(1) << 31),
+              "augment_mix_batch: row0 + B <= rows, B >= 1");
+  TORCH_CHECK(OH >= 1 && OW >= 1 && OH <= 512 && OW <= 512, "augment_mix_batch: OH, OW in [1, 512]");
+  TORCH_CHECK(A.size() == 3 && Bc.size() == 3, "augment_mix_batch: A, Bc of 3 floats");
+  TORCH_CHECK(kind >= 0 && kind <= 2, "augment_mix_batch: kind 0 (none), 1 (mixup) or 2 (cutmix)");
+  TORCH_CHECK(lam16 >= 0 && lam16 <= 65536, "augment_mix_batch: lam16 in [0, 65536]");
+  TORCH_CHECK(box.size() == 4 && box[0] >= 0 && box[1] >= 0 && box[2] >= 0 && box[3] >= 0 && box[0] <= OH &&
+                  box[1] <= OW && box[2] <= OH - box[0] && box[3] <= OW - box[1],
+              "augment_mix_batch: box (cy0, cx0, ch, cw) inside the OH x OW output");
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.dim() == 4 && x.size(0) == B && x.size(1) == 3 &&
+                  x.size(2) == OH && x.size(3) == OW && x.permute({0, 2, 3, 1}).is_contiguous() &&
+                  reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "augment_mix_batch: x bf16 [B, 3, OH, OW] channels_last, 16-byte aligned");
+  for (const at::Tensor* y : {&y_a, &y_b})
+    TORCH_CHECK(y->is_cuda() && y->scalar_type() == at::kLong && y->dim() == 1 && y->numel() == B &&
+                    y->is_contiguous() && y->get_device() == images.get_device(),
+                "augment_mix_batch: y_a, y_b int64 [B] contiguous on the images' device");
+  TORCH_CHECK(labels.get_device() == images.get_device() && plan.get_device() == images.get_device() &&
+                  x.get_device() == images.get_device(),
+              "augment_mix_batch: one device");
+  const float a[3] = {static_cast<float>(A[0]), static_cast<float>(A[1]), static_cast<float>(A[2])};
+  const float b[3] = {static_cast<float>(Bc[0]), static_cast<float>(Bc[1]), static_cast<float>(Bc[2])};
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(images.device());
+  check_hip(kdl::augment_mix_batch(images.data_ptr<uint8_t>(), labels.data_ptr<int64_t>(), n, static_cast<int>(H),
+                                   static_cast<int>(W), plan.data_ptr<int>(), row0, static_cast<int>(B),
+                                   static_cast<int>(OH), static_cast<int>(OW), a, b, static_cast<int>(kind),
+                                   static_cast<int>(lam16), static_cast<int>(box[0]), static_cast<int>(box[1]),
+                                   static_cast<int>(box[2]), static_cast<int>(box[3]), x.data_ptr(),
+                                   y_a.data_ptr<int64_t>(), y_b.data_ptr<int64_t>(), cur_stream()),
+            "augment_mix_batch");
+}
+
 at::Tensor auc_finalize(const at::Tensor& hist) {
   check_auc_hist(hist, "auc_finalize");
   const c10::hip::HIPGuardMasqueradingAsCUDA guard(hist.device());
@@ -1321,9 +1369,15 @@ void need_f32(const at::Tensor& t, int64_t numel, const char* what) {
 // x [Nb, C, H, W] channels_last (the last block's output); ws = (feat, part1, lrow, dl, dlT)
 void head_forward(const at::Tensor& x, const at::Tensor& w, const c10::optional<at::Tensor>& b, const at::Tensor& y,
                   at::Tensor feat, at::Tensor part1, at::Tensor lrow, at::Tensor dl, at::Tensor dlT,
-                  double label_smoothing) {
+                  double label_smoothing, const c10::optional<at::Tensor>& y_b, double mix_lam) {
   TORCH_CHECK(x.dim() == 4 && is_nhwc_dense(x), "head_forward: x must be [Nb, C, H, W] channels_last");
   TORCH_CHECK(label_smoothing >= 0.0 && label_smoothing < 1.0, "head_forward: label_smoothing in [0, 1)");
+  const bool pair = y_b.has_value() && y_b->defined();
+  TORCH_CHECK(pair ? (mix_lam >= 0.0 && mix_lam <= 1.0) : mix_lam == 1.0,
+              "head_forward: mix_lam in [0, 1], and 1 without y_b");
+  TORCH_CHECK(!pair || (y_b->is_cuda() && y_b->scalar_type() == at::kLong && y_b->is_contiguous() &&
+                        y_b->numel() == x.size(0) && y_b->get_device() == x.get_device()),
+              "head y_b: int64 [Nb] on x's device");
   const int64_t Nb = x.size(0), C = x.size(1), HW = x.size(2) * x.size(3);
   TORCH_CHECK(w.dim() == 2 && w.size(1) == C && w.is_contiguous(), "head_forward: w must be [L, C] contiguous");
   const int64_t L = w.size(0);
@@ -1343,7 +1397,8 @@ void head_forward(const at::Tensor& x, const at::Tensor& w, const c10::optional<
   check_hip(kdl::head_forward(x.data_ptr(), static_cast<int>(Nb), static_cast<int>(HW), static_cast<int>(C),
                               w.data_ptr(), opt_ptr(b), static_cast<int>(L), y.data_ptr<int64_t>(), feat.data_ptr(),
                               part1.data_ptr<float>(), lrow.data_ptr<float>(), dl.data_ptr(), dlT.data_ptr(),
-                              cur_stream(), static_cast<float>(label_smoothing)),
+                              cur_stream(), static_cast<float>(label_smoothing),
+                              pair ? y_b->data_ptr<int64_t>() : nullptr, static_cast<float>(mix_lam)),
             "head_forward");
 }
 
@@ -2370,6 +2425,15 @@ PYBIND11_MODULE(_C, m) {
         py::arg("images"), py::arg("labels"), py::arg("plan"), py::arg("row0"), py::arg("B"), py::arg("OH"),
         py::arg("OW"), py::arg("A"), py::arg("Bc"), py::arg("x"), py::arg("y"));
   m.def("augment_tile_rows", &kdl::augment_tile_rows, "output rows one augment_batch block produces");
+  m.def("augment_mix_batch", &augment_mix_batch,
+        "image input with Mixup / CutMix: as augment_batch, image b mixed with image B-1-b of the batch; kind 0 none, "
+        "1 mixup (weight lam16 / 65536 on the integer samples), 2 cutmix (box = (cy0, cx0, ch, cw) of the output comes "
+        "from the partner); y_a = labels[src_b], y_b = labels[src_{B-1-b}]; one launch",
+        py::arg("images"), py::arg("labels"), py::arg("plan"), py::arg("row0"), py::arg("B"), py::arg("OH"),
+        py::arg("OW"), py::arg("A"), py::arg("Bc"), py::arg("kind"), py::arg("lam16"), py::arg("box"), py::arg("x"),
+        py::arg("y_a"), py::arg("y_b"));
+  m.def("augment_mix_tile_rows", &kdl::augment_mix_tile_rows,
+        "output rows of each image one augment_mix_batch block produces");
   m.def("auc_rows_per_block", &kdl::auc_rows_per_block, "rows one auc_accumulate block counts in LDS for n rows");
   m.def("segment_reduce_adagrad", &segment_reduce_adagrad,
         "one-owner sync-free push: per-id gradient sums (segment_reduce) applied by Adagrad in the same launch");
@@ -2393,7 +2457,8 @@ PYBIND11_MODULE(_C, m) {
   m.def("head_lpad", [](int64_t L) { return kdl::head_lpad(static_cast<int>(L)); }, "row pitch of the head's dl");
   m.def("head_forward", &head_forward, "classifier head forward: mean pool + fc (MFMA) + softmax CE + dlogits",
         py::arg("x"), py::arg("w"), py::arg("b"), py::arg("y"), py::arg("feat"), py::arg("part1"), py::arg("lrow"),
-        py::arg("dl"), py::arg("dlT"), py::arg("label_smoothing") = 0.0);
+        py::arg("dl"), py::arg("dlT"), py::arg("label_smoothing") = 0.0, py::arg("y_b") = py::none(),
+        py::arg("mix_lam") = 1.0);
   m.def("head_backward", &head_backward, "classifier head backward: dfeat, dW, db (MFMA) + mean loss");
   m.def("stem7x7_fwd", &stem7x7_fwd, "ResNet stem 7x7/s2/p3 conv (224 -> 112, 3 -> 64 channels) with BN statistics epilogue");
   m.def("conv3x3_s2_dgrad", &conv3x3_s2_dgrad,

@@ -222,13 +222,21 @@ __device__ __forceinline__ float block_reduce(float v, float* red, bool is_max) 
 //   loss_n = lse - (1 - eps) z[y] - (eps / L) sum_l z[l]   (one more block sum over the LDS row)
 //   dl     = (softmax - (1 - eps) onehot - eps / L) * inv_n
 // eps == 0 launches the plain instantiation (head_forward): its code is the kernel as it was.
-template <bool SMOOTH>
+// PAIR: two labels per image (Mixup / CutMix), target lam * t(y) + (1 - lam) * t(y2):
+//   loss_n = lse - (1 - eps) (lam z[y] + (1 - lam) z[y2]) - (eps / L) sum_l z[l]
+//   dl     = (softmax - (1 - eps) (lam [l == y] + (1 - lam) [l == y2]) - eps / L) * inv_n
+// The weights are summed per class, so y == y2 carries lam + (1 - lam): where that sum is
+// exact, and at lam = 1, the row is the one-label kernel's, bit for bit.  A label outside
+// [0, L) in either slot: NaN loss, zero gradient row.  Without PAIR the code is the kernel
+// as it was (y2 and lam are not read).
+template <bool SMOOTH, bool PAIR = false>
 __global__ __launch_bounds__(256) void head_ce_kernel(const float* __restrict__ part1, int splits, int Nb, int L,
                                                       int Lp,
                                                       const bf16_t* __restrict__ bias,
                                                       const int64_t* __restrict__ y, float inv_n, float eps,
                                                       float* __restrict__ lrow, bf16_t* __restrict__ dl,
-                                                      bf16_t* __restrict__ dlT) {
+                                                      bf16_t* __restrict__ dlT,
+                                                      const int64_t* __restrict__ y2 = nullptr, float lam = 1.f) {
   extern __shared__ float z[];  // [L]
   __shared__ float red[4];
   const int n = blockIdx.x, t = threadIdx.x;
@@ -253,10 +261,26 @@ __global__ __launch_bounds__(256) void head_ce_kernel(const float* __restrict__ 
   // a label outside [0, L) (e.g. an ignore_index of -100) never indexes z: its
   // row's loss is NaN -- the step's mean loss turns NaN, loudly, as the
   // autograd head would have raised -- and its gradient row is zero
-  const bool ok = y64 >= 0 && y64 < L;
+  bool ok = y64 >= 0 && y64 < L;
+  int y2n = -1;
+  float wa = 1.f, wb = 0.f;  // PAIR only
+  if (PAIR) {
+    const int64_t b64 = y2[n];
+    ok = ok && b64 >= 0 && b64 < L;
+    y2n = ok ? static_cast<int>(b64) : -1;
+    wa = lam;
+    wb = 1.f - lam;
+  }
   const int yn = ok ? static_cast<int>(y64) : -1;
   if (t == 0) {
-    if (SMOOTH)
+    if (PAIR) {
+      float zm = 0.f;
+      if (ok) zm = yn == y2n ? (wa + wb) * z[yn] : wa * z[yn] + wb * z[y2n];
+      if (SMOOTH)
+        lrow[n] = ok ? __logf(se) + mx - hot * zm - unif * sz : __int_as_float(0x7fc00000);
+      else
+        lrow[n] = ok ? __logf(se) + mx - zm : __int_as_float(0x7fc00000);
+    } else if (SMOOTH)
       lrow[n] = ok ? __logf(se) + mx - hot * z[yn] - unif * sz : __int_as_float(0x7fc00000);
     else
       lrow[n] = ok ? __logf(se) + mx - z[yn] : __int_as_float(0x7fc00000);
@@ -264,7 +288,15 @@ __global__ __launch_bounds__(256) void head_ce_kernel(const float* __restrict__ 
   const float rse = 1.f / se;
   for (int l = t; l < Lp; l += 256) {  // dl rows padded to Lp (16-B rows for the backward's loads)
     float g;
-    if (SMOOTH)
+    if (PAIR) {
+      // the class's target weight, a selected value as the one-label kernel's (l == yn ? hot : 0)
+      const float tw = (l == yn ? wa : 0.f) + (l == y2n ? wb : 0.f);
+      const float ht = (l == yn || l == y2n) ? hot * tw : 0.f;
+      if (SMOOTH)
+        g = (l < L && ok) ? (__expf(z[l] - mx) * rse - ht - unif) * inv_n : 0.f;
+      else
+        g = (l < L && ok) ? (__expf(z[l] - mx) * rse - (l == yn || l == y2n ? tw : 0.f)) * inv_n : 0.f;
+    } else if (SMOOTH)
       g = (l < L && ok) ? (__expf(z[l] - mx) * rse - (l == yn ? hot : 0.f) - unif) * inv_n : 0.f;
     else
       g = (l < L && ok) ? (__expf(z[l] - mx) * rse - (l == yn ? 1.f : 0.f)) * inv_n : 0.f;
@@ -388,9 +420,10 @@ void head_splits(int Nb, int C, int L, int* s1, int* s2) {
 
 hipError_t head_forward(const void* x, int Nb, int HW, int C, const void* w, const void* b, int L, const int64_t* y,
                         void* feat, float* part1, float* lrow, void* dl, void* dlT, hipStream_t s,
-                        float label_smoothing) {
+                        float label_smoothing, const int64_t* y_b, float mix_lam) {
   if (Nb <= 0 || HW <= 0 || C % 8 || L <= 0 || L > 8192) return hipErrorInvalidValue;
   if (!(label_smoothing >= 0.f && label_smoothing < 1.f)) return hipErrorInvalidValue;
+  if (y_b && !(mix_lam >= 0.f && mix_lam <= 1.f)) return hipErrorInvalidValue;
   int s1, s2;
   head_splits(Nb, C, L, &s1, &s2);
   hipLaunchKernelGGL(head_pool_kernel, dim3(Nb, (C + 511) / 512), dim3(256), 0, s, static_cast<const bf16_t*>(x), HW,
@@ -399,6 +432,19 @@ hipError_t head_forward(const void* x, int Nb, int HW, int C, const void* w, con
   g.part = part1;
   HeadGemm none{};
   hipLaunchKernelGGL((head_gemm_kernel<false, false>), dim3(g.blocks), dim3(256), 0, s, g, none);
+  if (y_b) {  // the two-label instantiations (Mixup / CutMix); without y_b the launches below are as they were
+    const bf16_t* bb = static_cast<const bf16_t*>(b);
+    const float inv_n = 1.f / static_cast<float>(Nb);
+    if (label_smoothing > 0.f)
+      hipLaunchKernelGGL((head_ce_kernel<true, true>), dim3(Nb), dim3(256), L * sizeof(float), s, part1, s1, Nb, L,
+                         head_lpad(L), bb, y, inv_n, label_smoothing, lrow, static_cast<bf16_t*>(dl),
+                         static_cast<bf16_t*>(dlT), y_b, mix_lam);
+    else
+      hipLaunchKernelGGL((head_ce_kernel<false, true>), dim3(Nb), dim3(256), L * sizeof(float), s, part1, s1, Nb, L,
+                         head_lpad(L), bb, y, inv_n, 0.f, lrow, static_cast<bf16_t*>(dl), static_cast<bf16_t*>(dlT),
+                         y_b, mix_lam);
+    return hipGetLastError();
+  }
   if (label_smoothing > 0.f)
     hipLaunchKernelGGL(head_ce_kernel<true>, dim3(Nb), dim3(256), L * sizeof(float), s, part1, s1, Nb, L,
                        head_lpad(L), static_cast<const bf16_t*>(b), y, 1.f / static_cast<float>(Nb), label_smoothing,

@@ -435,6 +435,17 @@ int augment_tile_rows(int OH, int OW);  // output rows one block produces
 hipError_t augment_batch(const uint8_t* images, const int64_t* labels, int64_t n_img, int H, int W, const int* plan,
                          int64_t row0, int B, int OH, int OW, const float* A, const float* Bc, void* x, int64_t* y,
                          hipStream_t s);
+// Mixup / CutMix inside the input launch: output image b is mixed with image B-1-b of
+// the same batch (a block owns the pair and a row tile, resamples each source once and
+// writes both outputs).  kind 0 none, 1 Mixup with weight lam16 / 65536 (0..65536) on the
+// integer samples, 2 CutMix: the box (cy0, cx0, ch, cw) of the output, inside it, comes
+// from the partner.  y_a [B] = labels[src_b], y_b [B] = labels[src_{B-1-b}].  The box
+// must lie inside OH x OW (an empty one is allowed); the same limits as augment_batch.
+int augment_mix_tile_rows(int OH, int OW);  // output rows of each image one block produces
+hipError_t augment_mix_batch(const uint8_t* images, const int64_t* labels, int64_t n_img, int H, int W,
+                             const int* plan, int64_t row0, int B, int OH, int OW, const float* A, const float* Bc,
+                             int kind, int lam16, int cy0, int cx0, int ch, int cw, void* x, int64_t* y_a,
+                             int64_t* y_b, hipStream_t s);
 
 
 // ---- conv1x1.hip (ResNet 1x1 convs as MFMA GEMMs with fused BN prologue/epilogues)
@@ -527,7 +538,9 @@ hipError_t head_eval(const void* x, int Nb, int HW, int C, const void* w, const 
 int head_lpad(int L);  // dl's row pitch: L rounded up to 8
 hipError_t head_forward(const void* x, int Nb, int HW, int C, const void* w, const void* b, int L, const int64_t* y,
                         void* feat, float* part1, float* lrow, void* dl, void* dlT, hipStream_t s,
-                        float label_smoothing = 0.f);  // eps in [0, 1): targets (1 - eps) onehot + eps / L
+                        float label_smoothing = 0.f,  // eps in [0, 1): targets (1 - eps) onehot + eps / L
+                        const int64_t* y_b = nullptr,  // second labels [Nb]: the two-label CE kernel, the target
+                        float mix_lam = 1.f);          //   mix_lam * t(y) + (1 - mix_lam) * t(y_b), mix_lam in [0, 1]
 hipError_t head_backward(const void* feat, const void* w, const void* dl, const void* dlT, int Nb, int C, int L,
                          float* part2, void* dfeat, void* dW, void* db, const float* lrow, float* loss,
                          hipStream_t s);

@@ -21,6 +21,44 @@ and ``x[b, c, oy, ox] = bf16(fma(float(q), A[c], B[c]))`` with
 ``A = fp32(1/std)``, ``B = fp32(-mean/std)`` computed in fp64.  The reference
 evaluates ``q*A + B`` in fp64 -- exact for 8-bit ``q`` and fp32 ``A, B`` of
 comparable magnitude -- and rounds once to fp32, as the fma does.
+
+Mixup and CutMix (``augment_mix_reference``, the kernel ``augment_mix_batch``)
+-------------------------------------------------------------------------------
+Output image ``i`` is paired with image ``j = B-1-i`` of the same per-rank batch
+(for odd ``B`` the middle image pairs with itself).  A step has one ``kind`` in
+{0 none, 1 mixup, 2 cutmix}, one ``lam`` and, for CutMix, one box; they are drawn
+on the host (``data/plan.py``: ``InputPlan.mix_draw``), a pure function of
+(seed, step, rank).
+
+Mixup acts on the integer samples ``q`` above, before the normalisation (which is
+affine, so this is the mix of the normalised images):
+
+    lam16 = clamp(round(lam * 65536), 0, 65536)
+    m     = lam16 * q_i + (65536 - lam16) * q_j          # <= 255 * 65536 < 2^24
+    x     = bf16(fma(float(m), A16[c], B[c])),   A16 = A * 2^-16 (an exact scaling)
+
+``float(m)`` is exact.  The reference evaluates ``m * A16 + B`` in fp64 and rounds
+once to fp32: ``m`` is an integer below 2^24 and ``A16`` has 24 significant bits,
+so the product is exact in fp64 and spans at most 48 bits above ``ulp(A16)`` -- for
+every std <= 255 (``A >= 2^-8``) that lowest bit is 2^-47 or above, and for the
+ImageNet statistics the value stays below 2^3.  ``B`` is, as above, of comparable
+magnitude (``|B| <= 255 A``, its own lowest bit at or above the product's), so the
+sum has one carry bit more, 49 of fp64's 53: the fp64 value is exact, and its
+single rounding is the fma's.  With ``lam16 = 65536``,
+``m * A16 = q_i * A`` exactly, so the result is bit-equal to the unmixed image.
+
+CutMix: one box ``(cy0, cx0, ch, cw)`` in output coordinates, centre uniform over
+the output, sides ``round(OH sqrt(1 - lam))`` and ``round(OW sqrt(1 - lam))``,
+clipped to the image (``plan.cutmix_box``).  Inside the box, pixel ``(oy, ox)`` of
+output ``i`` is the augmented pixel ``(oy, ox)`` of image ``j`` (its own crop and
+flip); outside it is image ``i``'s own: a pure select, every value bit-equal to a
+value of the two unmixed images.
+
+Labels: ``y_a = labels[src_i]``, ``y_b = labels[src_j]`` and one fp32 ``lam_label``
+per step: Mixup ``lam16 / 65536`` (exact), CutMix the clipped box's weight
+``fp32(1 - ch*cw / (OH*OW))`` from fp64, kind none 1.  The loss of an image is
+``lam_label * CE(y_a) + (1 - lam_label) * CE(y_b)`` (csrc/head.hip, with label
+smoothing composed per term).
 """
 from __future__ import annotations
 
@@ -88,6 +126,61 @@ def augment_reference(images_u8: torch.Tensor, labels: torch.Tensor, plan_rows, 
     x = normalize_q(resample_q(images_u8, plan_rows, OH, OW), mean, std)  # [B, OH, OW, 3]
     src = plan_rows[:, 0].to(device=labels.device, dtype=torch.int64)
     return x.permute(0, 3, 1, 2), labels[src].to(torch.int64)
+
+
+def mix_lam_label(kind: int, lam16: int, box, OH: int, OW: int) -> float:
+    """The step's label weight as an fp32 value: Mixup ``lam16 / 65536``, CutMix
+    ``fp32(1 - ch*cw / (OH*OW))`` of the clipped box, kind none 1."""
+    if kind == 1:
+        return float(np.float32(lam16 / 65536.0))
+    if kind == 2:
+        return float(np.float32(1.0 - (int(box[2]) * int(box[3])) / float(OH * OW)))
+    return 1.0
+
+
+def check_mix(kind: int, lam16: int, box, OH: int, OW: int) -> None:
+    cy0, cx0, ch, cw = (int(v) for v in box)
+    if kind not in (0, 1, 2) or not 0 <= lam16 <= 65536:
+        raise ValueError(f"mix: kind 0, 1 or 2 and lam16 in [0, 65536], got kind {kind}, lam16 {lam16}")
+    if min(cy0, cx0, ch, cw) < 0 or cy0 + ch > OH or cx0 + cw > OW:
+        raise ValueError(f"mix: box {(cy0, cx0, ch, cw)} outside the {OH}x{OW} output")
+
+
+def augment_mix_reference(images_u8: torch.Tensor, labels: torch.Tensor, plan_rows, OH: int, OW: int, mean, std,
+                          kind: int, lam16: int = 65536, box=(0, 0, 0, 0)):
+    """``(x, y_a, y_b, lam_label)`` of the module docstring's Mixup / CutMix rule: ``x``
+    bf16 [B, 3, OH, OW] channels_last with image ``i`` mixed with image ``B-1-i``,
+    ``y_a = labels[src_i]``, ``y_b = labels[src_{B-1-i}]``, ``lam_label`` a float."""
+    if images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or images_u8.size(3) != 3:
+        raise ValueError(f"augment_mix_reference: images uint8 [n, H, W, 3], got {images_u8.dtype} "
+                         f"{tuple(images_u8.shape)}")
+    check_mix(kind, lam16, box, OH, OW)
+    plan_rows = torch.as_tensor(plan_rows)
+    q = resample_q(images_u8, plan_rows, OH, OW)  # [B, OH, OW, 3]
+    qj = q.flip(0)
+    if kind == 2:
+        cy0, cx0, ch, cw = (int(v) for v in box)
+        inside = torch.zeros(OH, OW, dtype=torch.bool, device=q.device)
+        inside[cy0:cy0 + ch, cx0:cx0 + cw] = True
+        l = torch.where(inside, 0, 65536)[None, :, :, None]
+    else:
+        l = lam16 if kind == 1 else 65536
+    m = l * q + (65536 - l) * qj
+    A, Bc = norm_coeffs(mean, std)
+    A16 = torch.from_numpy(np.ldexp(A, -16)).to(q.device).double()
+    x = (m.double() * A16 + torch.from_numpy(Bc).to(q.device).double()).float().bfloat16()
+    src = plan_rows[:, 0].to(device=labels.device, dtype=torch.int64)
+    y = labels[src].to(torch.int64)
+    return x.permute(0, 3, 1, 2), y, y.flip(0), mix_lam_label(kind, lam16, box, OH, OW)
+
+
+def augment_mix_batch(images_u8, labels, plan, row0: int, B: int, OH: int, OW: int, A, Bc, kind: int, lam16: int,
+                      box, x, y_a, y_b) -> None:
+    """The HIP path: one launch of ``kdl::augment_mix_batch`` on the current stream."""
+    from kubedl_amd.ops import _ext
+    _ext.load().augment_mix_batch(images_u8, labels, plan, int(row0), int(B), int(OH), int(OW),
+                                  [float(v) for v in A], [float(v) for v in Bc], int(kind), int(lam16),
+                                  [int(v) for v in box], x, y_a, y_b)
 
 
 def augment_batch(images_u8, labels, plan, row0: int, B: int, OH: int, OW: int, A, Bc, x, y) -> None:

@@ -30,6 +30,14 @@ the input independent of where that join sits and leaves the previous batch
 readable while the next is produced.
 
 On the CPU both modes call ``augment_reference`` (data/augment.py).
+
+Mixup / CutMix (``mix=MixConfig(...)``, training inputs only): ``next`` returns
+``(x, y_a, y_b, lam_label)`` instead of ``(x, y)``.  The step's kind, weight and box
+come from ``InputPlan.mix_draw(step)`` on the host and travel as kernel arguments of
+ONE ``augment_mix_batch`` launch in place of ``augment_batch`` (no extra pass over x,
+no device write, no sync); a step whose draw is "none" issues ``augment_batch`` as
+ever and returns ``(x, y, y, 1.0)``.  ``lam_label`` is a Python float.  On the CPU
+the mixed step is ``augment_mix_reference``.
 """
 from __future__ import annotations
 
@@ -42,8 +50,9 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from kubedl_amd.data.augment import augment_batch, augment_reference, norm_coeffs
-from kubedl_amd.data.plan import InputPlan
+from kubedl_amd.data.augment import (augment_batch, augment_mix_batch, augment_mix_reference, augment_reference,
+                                     mix_lam_label, norm_coeffs)
+from kubedl_amd.data.plan import MIX_NONE, InputPlan, MixConfig
 from kubedl_amd.data.shards import ImageShards
 
 RING = 3
@@ -79,7 +88,8 @@ class _Slot:
 
 class ShardInput:
     def __init__(self, shards: ImageShards, info, batch: int, image: int, seed: int = 0, mode: str = "auto",
-                 train: bool = True, workers: int = 4, resident_gb=None, max_batches: int = 0):
+                 train: bool = True, workers: int = 4, resident_gb=None, max_batches: int = 0,
+                 mix: MixConfig | None = None):
         if mode not in ("auto", "resident", "stream"):
             raise ValueError(f"ShardInput: mode {mode!r}")
         self.shards = shards
@@ -87,8 +97,9 @@ class ShardInput:
         self.hip = self.device.type == "cuda"
         self.batch, self.OH, self.OW = int(batch), int(image), int(image)
         self.plan = InputPlan(shards.count, shards.height, shards.width, info.world_size, info.rank, batch,
-                              seed=seed, train=train)
+                              seed=seed, train=train, mix=mix)
         self.train = train
+        self.mixing = self.plan.mix is not None  # next() then returns (x, y_a, y_b, lam_label)
         self.steps_per_epoch = self.plan.steps_per_epoch
         self.dropped = self.plan.dropped
         self.max_batches = int(max_batches)
@@ -104,6 +115,7 @@ class ShardInput:
         self.batches = 0
         self._x = [None, None]
         self._y = [None, None]
+        self._yb = [None, None]
         self._epoch = None        # epoch of the cached plan table
         self._rows = None         # its host rows
         self._d_rows = None       # its device copy (resident, GPU)
@@ -144,22 +156,40 @@ class ShardInput:
             x = torch.empty(self.batch, self.OH, self.OW, 3, dtype=torch.bfloat16, device=self.device)
             self._x[k] = x.permute(0, 3, 1, 2)
             self._y[k] = torch.empty(self.batch, dtype=torch.int64, device=self.device)
-        return self._x[k], self._y[k]
+            if self.mixing:
+                self._yb[k] = torch.empty(self.batch, dtype=torch.int64, device=self.device)
+        return self._x[k], self._y[k], self._yb[k]
+
+    def _produce(self, step: int, images, labels, d_plan, h_rows, r0: int):
+        """The batch of plan rows ``r0 .. r0 + batch - 1``: one launch on the GPU (the
+        mixed or the plain kernel, by the step's draw), the reference on the CPU."""
+        draw = self.plan.mix_draw(step, self.OH, self.OW)
+        if not self.hip:
+            rows = torch.from_numpy(h_rows[r0:r0 + self.batch])
+            if draw.kind == MIX_NONE:
+                x, y = augment_reference(images, labels, rows, self.OH, self.OW, self.shards.mean, self.shards.std)
+                return (x, y, y, 1.0) if self.mixing else (x, y)
+            return augment_mix_reference(images, labels, rows, self.OH, self.OW, self.shards.mean, self.shards.std,
+                                         draw.kind, draw.lam16, draw.box)
+        x, y, yb = self._out()
+        if draw.kind == MIX_NONE:
+            augment_batch(images, labels, d_plan, r0, self.batch, self.OH, self.OW, self.A, self.B, x, y)
+            return (x, y, y, 1.0) if self.mixing else (x, y)
+        augment_mix_batch(images, labels, d_plan, r0, self.batch, self.OH, self.OW, self.A, self.B, draw.kind,
+                          draw.lam16, draw.box, x, y, yb)
+        return x, y, yb, mix_lam_label(draw.kind, draw.lam16, draw.box, self.OH, self.OW)
 
     def _next_resident(self, step: int):
         e, r0 = self.plan.locate(step)
         rows = self._epoch_rows(e)
         if not self.hip:
-            return augment_reference(self.images, self.labels, torch.from_numpy(rows[r0:r0 + self.batch]),
-                                     self.OH, self.OW, self.shards.mean, self.shards.std)
+            return self._produce(step, self.images, self.labels, None, rows, r0)
         if self._d_rows is None:
             # once per epoch; from pinned memory, so the host does not wait for the stream to drain
             self._h_rows = torch.from_numpy(rows).pin_memory()
             self._d_rows = self._h_rows.to(self.device, non_blocking=True)
             self.plan_uploads += 1
-        x, y = self._out()
-        augment_batch(self.images, self.labels, self._d_rows, r0, self.batch, self.OH, self.OW, self.A, self.B, x, y)
-        return x, y
+        return self._produce(step, self.images, self.labels, self._d_rows, rows, r0)
 
     # ------------------------------------------------------------ stream
     def _gather_into(self, slot: _Slot, gidx: np.ndarray) -> None:
@@ -242,23 +272,22 @@ class ShardInput:
         self._expect = step + 1
         slot = self._slots[k]
         if not self.hip:
-            out = augment_reference(slot.images, slot.labels, slot.plan.clone(), self.OH, self.OW,
-                                    self.shards.mean, self.shards.std)
+            out = self._produce(step, slot.images, slot.labels, None, slot.plan.clone().numpy(), 0)
             self._free.put(k)
             return out
         cur = torch.cuda.current_stream(self.device)
         cur.wait_event(slot.copied)
-        x, y = self._out()
-        augment_batch(slot.d_images, slot.d_labels, slot.d_plan, 0, self.batch, self.OH, self.OW, self.A, self.B, x, y)
+        out = self._produce(step, slot.d_images, slot.d_labels, slot.d_plan, None, 0)
         slot.consumed = torch.cuda.Event()
         slot.consumed.record(cur)
         self._free.put(k)
-        return x, y
+        return out
 
     # ------------------------------------------------------------ public
     def next(self, step: int):
         """``(x bf16 [B, 3, OH, OW] channels_last, y int64 [B])`` of step ``step``,
-        ordered on the current stream."""
+        ordered on the current stream; with a mix configuration
+        ``(x, y_a, y_b, lam_label)`` (the module docstring)."""
         if self.mode == "resident":
             return self._next_resident(int(step))
         return self._next_stream(int(step))

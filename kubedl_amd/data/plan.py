@@ -28,6 +28,16 @@ central crop at the clamped ratio; drawn vectorised.  ``flip`` is
 Bernoulli(0.5).  The eval plan is the natural order, no flip, the central
 ``round(0.875 H) x round(0.875 W)`` box (256 stored, 224 out: an exact copy),
 ``n_own // batch`` full batches, the remainder dropped (``eval_dropped``).
+
+Mixup / CutMix (``MixConfig``, ``InputPlan.mix_draw``): one draw per STEP, from
+``numpy.random.Generator(PCG64([seed, step, rank, MIX_STREAM]))`` -- a key of four
+words, so never an epoch's generator -- in a fixed order: apply (against ``prob``),
+switch (against ``switch_prob``), the Beta(alpha, alpha) weight of each kind whose
+alpha is > 0, the box centre.  A pure function of (seed, step, rank) and the
+configuration, as the rows are: a resumed job redraws the same mixes.  The kind is
+CutMix when only its alpha is > 0 or when both are and ``switch < switch_prob``,
+else Mixup; none when ``apply >= prob`` or both alphas are 0.  What the draw means
+for the pixels and the labels is the rule of data/augment.py.
 """
 from __future__ import annotations
 
@@ -40,6 +50,58 @@ SCALE = (0.08, 1.0)
 RATIO = (3.0 / 4.0, 4.0 / 3.0)
 TRIES = 10
 EVAL_CROP = 0.875
+MIX_STREAM = 0x6D6978  # fourth key word of the per-step mix generator
+MIX_NONE, MIX_MIXUP, MIX_CUTMIX = 0, 1, 2
+
+
+@dataclass(frozen=True)
+class MixConfig:
+    """Batch mixing of the training input: ``mixup_alpha`` / ``cutmix_alpha`` are the
+    Beta parameters (0: that kind is off), ``prob`` the chance a step is mixed at all,
+    ``switch_prob`` the chance of CutMix where both kinds are on."""
+    mixup_alpha: float = 0.0
+    cutmix_alpha: float = 0.0
+    prob: float = 1.0
+    switch_prob: float = 0.5
+
+    def __post_init__(self):
+        if not (self.mixup_alpha >= 0.0 and self.cutmix_alpha >= 0.0):
+            raise ValueError(f"MixConfig: alphas >= 0, got {self.mixup_alpha}, {self.cutmix_alpha}")
+        if not (0.0 <= self.prob <= 1.0 and 0.0 <= self.switch_prob <= 1.0):
+            raise ValueError(f"MixConfig: prob and switch_prob in [0, 1], got {self.prob}, {self.switch_prob}")
+
+    @property
+    def enabled(self) -> bool:
+        return self.mixup_alpha > 0.0 or self.cutmix_alpha > 0.0
+
+
+@dataclass(frozen=True)
+class MixDraw:
+    """One step's mix: ``kind`` (MIX_*), the drawn ``lam``, its 16-bit fixed-point form
+    ``lam16`` (Mixup's pixel weight) and the clipped CutMix box ``(cy0, cx0, ch, cw)``
+    in output coordinates (empty unless the kind is CutMix)."""
+    kind: int = MIX_NONE
+    lam: float = 1.0
+    lam16: int = 65536
+    box: tuple = (0, 0, 0, 0)
+
+
+def lam_to_16(lam: float) -> int:
+    """``clamp(round(lam * 65536), 0, 65536)``."""
+    return int(min(max(int(np.rint(lam * 65536.0)), 0), 65536))
+
+
+def cutmix_box(lam: float, uy: float, ux: float, OH: int, OW: int):
+    """The box of sides ``round(OH sqrt(1 - lam))``, ``round(OW sqrt(1 - lam))`` centred
+    at ``(floor(uy OH), floor(ux OW))``, clipped to the output: ``(cy0, cx0, ch, cw)``."""
+    s = math.sqrt(max(1.0 - lam, 0.0))
+    out = []
+    for u, n in ((uy, OH), (ux, OW)):
+        side = int(np.rint(n * s))
+        lo = min(int(u * n), n - 1) - side // 2
+        a, b = min(max(lo, 0), n), min(max(lo + side, 0), n)
+        out.append((a, b - a))
+    return out[0][0], out[1][0], out[0][1], out[1][1]
 
 
 def owned_count(N: int, world: int, rank: int) -> int:
@@ -126,9 +188,10 @@ class InputPlan:
     epoch ``e``, ``locate(step)`` says where a step's batch lies in it."""
 
     def __init__(self, count: int, height: int, width: int, world: int, rank: int, batch: int, seed: int = 0,
-                 train: bool = True):
+                 train: bool = True, mix: MixConfig | None = None):
         if not (0 <= rank < world) or batch < 1:
             raise ValueError(f"InputPlan: rank {rank} of world {world}, batch {batch}")
+        self.mix = mix if (mix is not None and mix.enabled and train) else None  # evaluation is never mixed
         self.count, self.height, self.width = int(count), int(height), int(width)
         self.world, self.rank, self.batch, self.seed, self.train = int(world), int(rank), int(batch), int(seed), train
         self.n_own = owned_count(self.count, self.world, self.rank)
@@ -168,3 +231,20 @@ class InputPlan:
         for tests and the per-batch path; ``ShardInput`` caches the epoch)."""
         e, r0 = self.locate(step)
         return self.epoch(e).rows[r0:r0 + self.batch]
+
+    def mix_draw(self, step: int, OH: int, OW: int) -> MixDraw:
+        """The mix of step ``step``'s batch for an ``OH x OW`` output (kind none without a
+        mix configuration)."""
+        m = self.mix
+        if m is None:
+            return MixDraw()
+        rng = np.random.Generator(np.random.PCG64([self.seed, int(step), self.rank, MIX_STREAM]))
+        apply, switch = rng.random(), rng.random()
+        lam_m = float(rng.beta(m.mixup_alpha, m.mixup_alpha)) if m.mixup_alpha > 0 else 1.0
+        lam_c = float(rng.beta(m.cutmix_alpha, m.cutmix_alpha)) if m.cutmix_alpha > 0 else 1.0
+        uy, ux = rng.random(), rng.random()
+        if not apply < m.prob:
+            return MixDraw()
+        if m.cutmix_alpha > 0 and (m.mixup_alpha <= 0 or switch < m.switch_prob):
+            return MixDraw(MIX_CUTMIX, lam_c, 65536, cutmix_box(lam_c, uy, ux, OH, OW))
+        return MixDraw(MIX_MIXUP, lam_m, lam_to_16(lam_m))

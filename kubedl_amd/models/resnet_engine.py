@@ -122,6 +122,15 @@ def add_eval_totals(totals: torch.Tensor, loss_row: torch.Tensor, rank_row: torc
                            torch.tensor(float(loss_row.numel()), dtype=torch.float64, device=totals.device)])
 
 
+def mixed_cross_entropy(logits, y, y_b=None, mix_lam: float = 1.0, label_smoothing: float = 0.0):
+    """The training loss on torch ops: ``CE(y)``, or with second labels (Mixup /
+    CutMix) ``mix_lam * CE(y) + (1 - mix_lam) * CE(y_b)``, the smoothing in each term."""
+    loss = F.cross_entropy(logits, y, label_smoothing=label_smoothing)
+    if y_b is None:
+        return loss
+    return mix_lam * loss + (1.0 - mix_lam) * F.cross_entropy(logits, y_b, label_smoothing=label_smoothing)
+
+
 def torch_head_eval(fmap, w, b, y, totals, logits=None):
     """Pool -> fc -> per-image loss and label rank in torch ops, with the
     rounding points of csrc/head.hip (bf16 pooled features, fp32 logits)."""
@@ -547,10 +556,12 @@ class HipKernels:
                 and fmap.is_contiguous(memory_format=torch.channels_last) and n % 8 == 0 and c % 8 == 0
                 and L <= 8192 and y.dtype == torch.int64)
 
-    def head(self, fmap, w, b, y, dw, db, label_smoothing: float = 0.0):
+    def head(self, fmap, w, b, y, dw, db, label_smoothing: float = 0.0, y_b=None, mix_lam: float = 1.0):
         """Pool -> fc -> softmax CE -> backward on csrc/head.hip: (loss [1],
         dfeat [n, c] bf16); dW / db written into ``dw`` / ``db``.
-        ``label_smoothing`` > 0: the smoothed instantiation of the CE kernel."""
+        ``label_smoothing`` > 0: the smoothed instantiation of the CE kernel.
+        ``y_b`` (Mixup / CutMix): the two-label instantiation, the target
+        ``mix_lam * t(y) + (1 - mix_lam) * t(y_b)``; without it today's launch."""
         n, c = fmap.shape[:2]
         L = w.shape[0]
         key = ("head", n, c, L)
@@ -564,8 +575,13 @@ class HipKernels:
                                         dlT=torch.empty(L, n, **bf), part2=torch.empty(s2 * n * c, **f32),
                                         dfeat=torch.empty(n, c, **bf))
         yc = y if y.is_contiguous() else y.contiguous()
-        self.ext.head_forward(fmap, w, b, yc, ws["feat"], ws["part1"], ws["lrow"], ws["dl"], ws["dlT"],
-                              float(label_smoothing))
+        if y_b is None:
+            self.ext.head_forward(fmap, w, b, yc, ws["feat"], ws["part1"], ws["lrow"], ws["dl"], ws["dlT"],
+                                  float(label_smoothing))
+        else:
+            self.ext.head_forward(fmap, w, b, yc, ws["feat"], ws["part1"], ws["lrow"], ws["dl"], ws["dlT"],
+                                  float(label_smoothing), y_b if y_b.is_contiguous() else y_b.contiguous(),
+                                  float(mix_lam))
         loss = torch.empty(1, dtype=torch.float32, device=fmap.device)  # fresh per step (returned)
         self.ext.head_backward(ws["feat"], w, ws["dl"], ws["dlT"], ws["part2"], ws["dfeat"], dw, db, ws["lrow"],
                                loss)
@@ -1299,17 +1315,20 @@ class ResNetEngine:
         return self.K.head_eval(fmap, m.fc.weight, m.fc.bias, y, totals, logits)
 
     # ------------------------------------------------------------------ step
-    def forward_backward(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
-        """One training forward + backward; returns the (detached) loss."""
+    def forward_backward(self, x: torch.Tensor, y: torch.Tensor, y_b: torch.Tensor | None = None,
+                         mix_lam: float = 1.0) -> torch.Tensor:
+        """One training forward + backward; returns the (detached) loss.  ``y_b`` /
+        ``mix_lam`` (Mixup / CutMix): the loss is ``mix_lam * CE(y) + (1 - mix_lam) * CE(y_b)``,
+        label smoothing composed per term."""
         m = self.model
         feat_map = self.forward(x)
         n, c, h, w = feat_map.shape
         head = getattr(self.K, "head", None)
-        if head is not None and self.K.head_ok(feat_map, m.fc.weight, y):
+        if head is not None and self.K.head_ok(feat_map, m.fc.weight, y) and (y_b is None or y_b.dtype == torch.int64):
             # csrc/head.hip: pool + fc + softmax CE + their backward, dW / db straight
             # into the gradient buffer (no autograd, no vendor GEMM)
             loss, dfeat = head(feat_map, m.fc.weight, m.fc.bias, y, self._g(m.fc.weight), self._g(m.fc.bias),
-                               self.label_smoothing)
+                               self.label_smoothing, *(() if y_b is None else (y_b, mix_lam)))
             self.on_ready(m.fc.weight)
             self.on_ready(m.fc.bias)
             self.backward(dfeat, h * w)
@@ -1319,7 +1338,7 @@ class ResNetEngine:
             fcw = m.fc.weight.detach().requires_grad_(True)
             fcb = m.fc.bias.detach().requires_grad_(True)
             logits = F.linear(feat.to(fcw.dtype), fcw, fcb)
-            loss = F.cross_entropy(logits.float(), y, label_smoothing=self.label_smoothing)
+            loss = mixed_cross_entropy(logits.float(), y, y_b, mix_lam, self.label_smoothing)
             dfeat, dfcw, dfcb = torch.autograd.grad(loss, (feat, fcw, fcb))
         with torch.no_grad():
             self._g(m.fc.weight).copy_(dfcw)

@@ -38,6 +38,12 @@ per-chunk norm partials, then the trust-ratio update); ``--lr-schedule`` /
 (``ops/lr_schedule.py``), passed as a kernel argument; ``--label-smoothing``
 smooths the training loss in the head kernel.  The defaults (``sgd``, constant
 0.1, no smoothing) are the run the worker always did.
+
+``--mixup-alpha`` / ``--cutmix-alpha`` (with ``--data``; ``--mix-prob``,
+``--mix-switch-prob``) mix image ``i`` of each training batch with image
+``B-1-i``: the input launch becomes ``augment_mix_batch`` and the head takes two
+labels and the step's weight (``data/augment.py`` has the rule).  The step's mix
+is a function of (seed, step, rank); evaluation is never mixed.
 """
 from __future__ import annotations
 
@@ -250,8 +256,12 @@ class ResNetTrainer:
 
     def _step_body(self) -> torch.Tensor:
         """The step's device work: returns the loss."""
+        y_b, lam = None, 1.0
         if self.input is not None:
-            self.x, self.y = self.input.next(self.steps_done)
+            batch = self.input.next(self.steps_done)
+            self.x, self.y = batch[:2]
+            if len(batch) == 4:  # a mixing input (Mixup / CutMix): second labels and the step's label weight
+                y_b, lam = batch[2:]
         if self.lr_schedule != "constant" or self.lr_warmup_steps > 0:
             # a kernel argument of the optimizer launch: no device write, no sync
             self.opt.lr = lr_at(self.steps_done, peak=self.peak_lr, kind=self.lr_schedule,
@@ -261,11 +271,14 @@ class ResNetTrainer:
         self.space.zero_grad()
         with trace_range("forward_backward"):
             if self.engine is not None:
-                loss = self.engine.forward_backward(self.x, self.y)
+                loss = self.engine.forward_backward(self.x, self.y, y_b, lam)
                 self.space.mark_packed()  # gradients were written into the flat buffer
             else:
                 out = self.model(self.x)
                 loss = F.cross_entropy(out.float(), self.y, label_smoothing=self.label_smoothing)
+                if y_b is not None:  # lam * CE(y_a) + (1 - lam) * CE(y_b), the smoothing in each term
+                    loss = lam * loss + (1.0 - lam) * F.cross_entropy(out.float(), y_b,
+                                                                      label_smoothing=self.label_smoothing)
                 loss.backward()
         with trace_range("allreduce_wait"):
             self.ddp.finish()
@@ -409,9 +422,13 @@ def run(args) -> dict:
     def shard_input(shards, train, max_batches=0):
         if tr.num_classes < shards.classes:
             raise ValueError(f"{shards.dir}: {shards.classes} classes, the model has {tr.num_classes}")
+        mix = None
+        if train and (args.mixup_alpha > 0 or args.cutmix_alpha > 0):  # the training input only: evaluation is never mixed
+            from kubedl_amd.data.plan import MixConfig
+            mix = MixConfig(args.mixup_alpha, args.cutmix_alpha, args.mix_prob, args.mix_switch_prob)
         return ShardInput(shards, info, args.batch, args.image, seed=args.data_seed, mode=args.data_mode,
                           train=train, workers=args.data_workers, resident_gb=args.data_resident_gb,
-                          max_batches=max_batches)
+                          max_batches=max_batches, mix=mix)
     train_in = shard_input(train_shards, True) if train_shards is not None and not args.eval_only else None
     eval_in = shard_input(eval_shards, False, E) if eval_shards is not None else None
     inputs = [i for i in (train_in, eval_in) if i is not None]
@@ -585,6 +602,14 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--lr-end", type=float, default=0.0, help="learning rate at the end of the decay")
     ap.add_argument("--label-smoothing", type=float, default=0.0,
                     help="smoothing of the training loss's targets; evaluation stays the plain cross-entropy")
+    ap.add_argument("--mixup-alpha", type=float, default=0.0,
+                    help="with --data: Mixup of each image with image B-1-i of its batch, weight ~ Beta(alpha, alpha), "
+                         "inside the input launch; 0: off")
+    ap.add_argument("--cutmix-alpha", type=float, default=0.0,
+                    help="with --data: CutMix with the same partner, box area 1 - lam, lam ~ Beta(alpha, alpha); 0: off")
+    ap.add_argument("--mix-prob", type=float, default=1.0, help="chance that a step is mixed at all")
+    ap.add_argument("--mix-switch-prob", type=float, default=0.5,
+                    help="chance of CutMix instead of Mixup where both alphas are > 0")
     return ap
 
 
@@ -604,6 +629,12 @@ def parse_args(argv=None):
         ap.error("--data-workers >= 1")
     if not 0.0 <= args.label_smoothing < 1.0:
         ap.error("--label-smoothing in [0, 1)")
+    if not (args.mixup_alpha >= 0.0 and args.cutmix_alpha >= 0.0):
+        ap.error("--mixup-alpha and --cutmix-alpha >= 0")
+    if not (0.0 <= args.mix_prob <= 1.0 and 0.0 <= args.mix_switch_prob <= 1.0):
+        ap.error("--mix-prob and --mix-switch-prob in [0, 1]")
+    if (args.mixup_alpha > 0 or args.cutmix_alpha > 0) and not args.data:
+        ap.error("--mixup-alpha / --cutmix-alpha mix the batches of the image input: they need --data")
     if args.lr_warmup_steps < 0:
         ap.error("--lr-warmup-steps >= 0")
     return args
