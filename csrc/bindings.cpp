@@ -673,6 +673,72 @@ void gbdt_contribs(const at::Tensor& X, const at::Tensor& paths, const at::Tenso
             "gbdt_contribs");
 }
 
+// hist int64 [counters] += the mask histogram of X's rows over the mask table (csrc/gbdt_iv.hip).  table int32
+// [slots, 4]; chunk_off, cnt_off int32 [chunks + 1]: the slots and the counters of each chunk
+void gbdt_path_masks(const at::Tensor& X, const at::Tensor& table, const at::Tensor& chunk_off,
+                     const at::Tensor& cnt_off, const at::Tensor& hist) {
+  TORCH_CHECK(X.is_cuda() && X.scalar_type() == at::kFloat && X.dim() == 2 && X.is_contiguous() && X.size(1) >= 1,
+              "gbdt_path_masks: X must be a contiguous fp32 [N, F] GPU tensor");
+  TORCH_CHECK(X.size(1) <= (1 << 20), "gbdt_path_masks: at most 2^20 features");
+  TORCH_CHECK(table.is_cuda() && table.scalar_type() == at::kInt && table.dim() == 2 && table.size(1) == 4 &&
+                  table.is_contiguous() && table.numel() < (int64_t{1} << 31),
+              "gbdt_path_masks: table must be a contiguous int32 [slots, 4] GPU tensor");
+  for (const at::Tensor* p : {&chunk_off, &cnt_off})
+    TORCH_CHECK(p->is_cuda() && p->scalar_type() == at::kInt && p->dim() == 1 && p->is_contiguous() &&
+                    p->numel() >= 1 && p->numel() == chunk_off.numel(),
+                "gbdt_path_masks: chunk_off and cnt_off must be contiguous int32 [chunks + 1] GPU tensors");
+  TORCH_CHECK(hist.is_cuda() && hist.scalar_type() == at::kLong && hist.dim() == 1 && hist.is_contiguous() &&
+                  hist.numel() < (int64_t{1} << 31),
+              "gbdt_path_masks: hist must be a contiguous int64 [counters] GPU tensor, fewer than 2^31");
+  TORCH_CHECK(table.device() == X.device() && chunk_off.device() == X.device() && cnt_off.device() == X.device() &&
+                  hist.device() == X.device(),
+              "gbdt_path_masks: tensors on different devices");
+  if (X.size(0) == 0 || chunk_off.numel() == 1 || hist.numel() == 0) return;
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(X.device());
+  check_hip(kdl::gbdt_path_masks(X.data_ptr<float>(), X.size(0), static_cast<int>(X.size(1)),
+                                 table.data_ptr<int32_t>(), static_cast<int>(table.size(0)),
+                                 chunk_off.data_ptr<int32_t>(), cnt_off.data_ptr<int32_t>(),
+                                 static_cast<int>(chunk_off.numel() - 1), hist.numel(), hist.data_ptr<int64_t>(),
+                                 cur_stream()),
+            "gbdt_path_masks");
+}
+
+// out [N, K, F + 1] = the explain table's interventional contributions of X's rows, bias[k] in the last
+// column (csrc/gbdt_iv.hip).  table int32 [slots, 4]; chunk_off int32 [chunks + 1]; class_chunk int32 [K + 1]
+void gbdt_contribs_iv(const at::Tensor& X, const at::Tensor& table, const at::Tensor& chunk_off,
+                      const at::Tensor& class_chunk, const at::Tensor& bias, int64_t K, const at::Tensor& out) {
+  TORCH_CHECK(X.is_cuda() && X.scalar_type() == at::kFloat && X.dim() == 2 && X.is_contiguous() && X.size(1) >= 1,
+              "gbdt_contribs_iv: X must be a contiguous fp32 [N, F] GPU tensor");
+  TORCH_CHECK(X.size(1) < (1 << 20), "gbdt_contribs_iv: fewer than 2^20 features");
+  TORCH_CHECK(1 <= K && K <= 32, "gbdt_contribs_iv: 1 <= K <= 32");
+  TORCH_CHECK(table.is_cuda() && table.scalar_type() == at::kInt && table.dim() == 2 && table.size(1) == 4 &&
+                  table.is_contiguous() && table.numel() < (int64_t{1} << 31),
+              "gbdt_contribs_iv: table must be a contiguous int32 [slots, 4] GPU tensor");
+  TORCH_CHECK(chunk_off.is_cuda() && chunk_off.scalar_type() == at::kInt && chunk_off.dim() == 1 &&
+                  chunk_off.is_contiguous() && chunk_off.numel() >= 1,
+              "gbdt_contribs_iv: chunk_off must be a contiguous int32 [chunks + 1] GPU tensor");
+  TORCH_CHECK(class_chunk.is_cuda() && class_chunk.scalar_type() == at::kInt && class_chunk.dim() == 1 &&
+                  class_chunk.is_contiguous() && class_chunk.numel() == K + 1,
+              "gbdt_contribs_iv: class_chunk must be a contiguous int32 [K + 1] GPU tensor");
+  TORCH_CHECK(bias.is_cuda() && bias.scalar_type() == at::kFloat && bias.dim() == 1 && bias.is_contiguous() &&
+                  bias.numel() == K,
+              "gbdt_contribs_iv: bias must be a contiguous fp32 [K] GPU tensor");
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kFloat && out.dim() == 3 && out.is_contiguous() &&
+                  out.size(0) == X.size(0) && out.size(1) == K && out.size(2) == X.size(1) + 1,
+              "gbdt_contribs_iv: out must be a contiguous fp32 [N, K, F + 1] GPU tensor");
+  TORCH_CHECK(table.device() == X.device() && chunk_off.device() == X.device() &&
+                  class_chunk.device() == X.device() && bias.device() == X.device() && out.device() == X.device(),
+              "gbdt_contribs_iv: tensors on different devices");
+  if (X.size(0) == 0) return;
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(X.device());
+  check_hip(kdl::gbdt_contribs_iv(X.data_ptr<float>(), X.size(0), static_cast<int>(X.size(1)),
+                                  table.data_ptr<int32_t>(), static_cast<int>(table.size(0)),
+                                  chunk_off.data_ptr<int32_t>(), static_cast<int>(chunk_off.numel() - 1),
+                                  class_chunk.data_ptr<int32_t>(), bias.data_ptr<float>(), static_cast<int>(K),
+                                  out.data_ptr<float>(), cur_stream()),
+            "gbdt_contribs_iv");
+}
+
 // out [N, K, F + 1, F + 1] = the per-feature path table's SHAP interaction values of X's rows, bias[k] at
 // [F, F] (csrc/gbdt_interactions.hip).  paths int32 [slots, 4]; chunk_off int32 [chunks + 1]; feat_chunk
 // int32 [K * F + 1]
@@ -2365,7 +2431,18 @@ PYBIND11_MODULE(_C, m) {
   m.def("gbdt_heap_nodes", &gbdt_heap_nodes, "the grower's [4, heap] arrays -> packed forest nodes, on the device");
   m.def("gbdt_cover", &gbdt_cover, "cover pass: counts[node] += rows of X reaching the node, trees [t0, t1)");
   m.def("gbdt_contribs", &gbdt_contribs, "exact TreeSHAP of a path table: out[N, K, F + 1]");
-  m.def("gbdt_interactions", &gbdt_interactions, "SHAP interaction values of a per-feature path table: out[N, K, F + 1, F + 1]");
+  m.def("gbdt_path_masks", &gbdt_path_masks, "mask histogram of background rows over a mask table: hist[counters] +=");
+  m.def("gbdt_contribs_iv", &gbdt_contribs_iv, "interventional TreeSHAP of an explain table: out[N, K, F + 1]");
+  m.def("gbdt_path_masks_chunk_slots", &kdl::gbdt_path_masks_chunk_slots, "mask-table slots per LDS chunk (whole paths)");
+  m.def("gbdt_path_masks_chunk_counters", &kdl::gbdt_path_masks_chunk_counters,
+        "int32 counters per LDS chunk of the mask-histogram kernel (the sum of 2^m over a chunk's paths)");
+  m.def("gbdt_path_masks_rows_per_block", &kdl::gbdt_path_masks_rows_per_block,
+        "rows per block of the mask-histogram kernel for F features (0: rows not staged in LDS)");
+  m.def("gbdt_contribs_iv_chunk_slots", &kdl::gbdt_contribs_iv_chunk_slots,
+        "explain-table slots per LDS chunk of the interventional kernel (whole table paths)");
+  m.def("gbdt_contribs_iv_rows_per_block", &kdl::gbdt_contribs_iv_rows_per_block,
+        "rows per block of the interventional kernel for F features (0: nothing staged in LDS)");
+  m.def("gbdt_interactions", &gbdt_interactions,"SHAP interaction values of a per-feature path table: out[N, K, F + 1, F + 1]");
   m.def("gbdt_interactions_chunk_slots", &kdl::gbdt_interactions_chunk_slots,
         "16-byte path slots per LDS chunk of the interaction kernel (whole paths)");
   m.def("gbdt_interactions_rows_per_block", &kdl::gbdt_interactions_rows_per_block,

@@ -293,6 +293,25 @@ hipError_t gbdt_contribs(const float* X, int64_t N, int F, const int32_t* paths,
 int gbdt_contribs_chunk_slots();          // 16-byte path slots per LDS chunk (whole paths)
 int gbdt_contribs_rows_per_block(int F);  // 256 / 128 / 64, or 0: rows and accumulators not in LDS
 
+// ---- gbdt_iv.hip (interventional TreeSHAP: set_background(interventional=True) / predict_contribs)
+// hist[first counter of the path + mask(row)] += 1 for every row of X and every path of the mask table
+// (layouts: gbdt_iv.hip's header; table int32 [num_slots, 4]; chunk c holds slots [chunk_off[c],
+// chunk_off[c + 1]) and counters [cnt_off[c], cnt_off[c + 1])).  hist: int64 [num_counters]; integer atomics
+hipError_t gbdt_path_masks(const float* X, int64_t N, int F, const int32_t* table, int num_slots,
+                           const int32_t* chunk_off, const int32_t* cnt_off, int num_chunks, int64_t num_counters,
+                           int64_t* hist, hipStream_t s);
+// out [N, K, F + 1] = interventional TreeSHAP of the explain table (paths with their {mask, weight} records;
+// chunk_off int32 [num_chunks + 1], class_chunk int32 [K + 1]); the last column is bias[k].  Every element
+// is written; one lane owns a row, no atomics; 1 <= K <= 32
+hipError_t gbdt_contribs_iv(const float* X, int64_t N, int F, const int32_t* table, int num_slots,
+                            const int32_t* chunk_off, int num_chunks, const int32_t* class_chunk, const float* bias,
+                            int K, float* out, hipStream_t s);
+int gbdt_path_masks_chunk_slots();          // mask-table slots per LDS chunk (whole paths)
+int gbdt_path_masks_chunk_counters();       // int32 counters per LDS chunk (the sum of 2^m over its paths)
+int gbdt_path_masks_rows_per_block(int F);  // 256 / 128 / 64, or 0: rows not staged in LDS
+int gbdt_contribs_iv_chunk_slots();         // explain-table slots per LDS chunk (whole table paths)
+int gbdt_contribs_iv_rows_per_block(int F);  // 256 / 128 / 64, or 0: rows and accumulators not in LDS
+
 // ---- gbdt_interactions.hip (SHAP interaction values: HistGBDT.predict_interactions)
 // out [N, K, F + 1, F + 1] = the Shapley interaction index of every feature pair, the diagonal so that
 // the last axis sums to gbdt_contribs' result, bias[k] at [F, F] (formula and per-feature table layout:

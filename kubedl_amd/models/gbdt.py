@@ -66,6 +66,36 @@ feature f_l, zero fraction z_l and o_l in {0, 1} the interval test on the row):
 Every integrand has degree at most ``m - 1``: Gauss-Legendre with ``ceil(m / 2)``
 nodes is exact for ``W_i`` and ``W_ij``.
 
+Interventional contributions: ``set_background(X, interventional=True)`` keeps the
+background rows and ``predict_contribs(X, perturbation="interventional")`` returns the
+interventional (marginal) TreeSHAP values, fp32 [N, K, F + 1] (csrc/gbdt_iv.hip: a
+mask-histogram kernel over the background and an explain kernel over the compacted
+histogram; on CPU ``_contribs_iv_torch``, fp64 over the background rows themselves,
+rounded once).  The definition, shared by both paths and by the tests, in the notation
+of csrc/gbdt_shap.hip (a path of class k: leaf value v, m <= 10 merged elements with
+feature f_l and o_l(r) in {0, 1} the interval test on row r; NaN fails every left and
+passes every right condition; ``full = 2^m - 1``; ``mask(r)`` has bit l = o_l(r)):
+
+* For a row x and a background row z the hybrid row ``h(S)`` takes the features in S
+  from x and the others from z.  The path's game ``S -> v * [h(S) reaches the leaf]`` is
+  a conjunction.  With ``mx = mask(x)``, ``mz = mask(z)``: if ``(mx | mz) != full`` the
+  path contributes nothing; otherwise let ``D = mx & ~mz`` with ``a = popcount(D)`` and
+  ``E = mz & ~mx`` with ``b = popcount(E)``: every element in D gets
+  ``+v (a-1)! b! / (a+b)!``, every element in E gets ``-v a! (b-1)! / (a+b)!``, elements
+  with both bits set are dummies.
+* ``phi[n, k, f_l]`` is the mean over the background rows (all ranks') of the sum over
+  class k's paths.
+* ``phi[n, k, F] = base + mean_z f_k(z)``: per path ``v * count(mask == full) / B``, paths
+  with ``m = 0`` add v; summed in fp64 on the host.
+* So the last axis sums to ``predict(X, output_margin=True)``, a feature no path of the
+  class uses gets exactly 0, and x equal to a background row contributes exactly 0 for
+  that z.
+
+For a fixed path and x a background row matters only through ``mz``: the GPU path
+reduces the background once to ``hist[path][mask]`` (int64 counts, 2^m per path, merged
+over the ranks by an integer all-reduce) and walks each path's distinct masks with
+``w = count / B``; its cost per row does not depend on B.
+
 Learning to rank: objectives ``rank:pairwise`` and ``rank:ndcg`` (LambdaMART).  On the
 GPU the gradient is the pair kernels of csrc/gbdt_rank.hip over a work plan built
 once per ``fit``; on CPU the same definition on torch ops in fp64, rounded once.  The
@@ -198,6 +228,8 @@ class HistGBDT:
         self._cover_cache = None  # (forest key, int64 covers [num_nodes], background F): set_background()
         self._paths_cache = None  # (key, path table): _path_table()
         self._pairs_cache = None  # (the same key, per-feature path table): _pair_table()
+        self._iv_bg = None  # (forest key, background rows, rows over all ranks): set_background(interventional=True)
+        self._iv_cache = None  # (the path table's key, explain table): _iv_table()
 
     # ------------------------------------------------------------ quantisation
     def fit_cuts(self, X: torch.Tensor, sample: int = 65536, seed: int = 0) -> None:
@@ -970,13 +1002,19 @@ class HistGBDT:
         return margin[:, 0]
 
     # ------------------------------------------------------------ feature contributions
-    def set_background(self, X: torch.Tensor) -> torch.Tensor:
+    def set_background(self, X: torch.Tensor, interventional: bool = False) -> torch.Tensor:
         """The covers ``predict_contribs`` weighs unknown features with: per node of
         the packed forest, the number of rows of ``X`` (this rank's shard; summed over
         the ranks of a process group) that reach it under ``predict``'s routing.
         int64 [num_nodes], kept beside the forest cache (not saved with the model) and
         dropped when ``trees`` is replaced.  On the GPU this is the cover kernel of
-        csrc/gbdt_shap.hip, on CPU a torch traversal."""
+        csrc/gbdt_shap.hip, on CPU a torch traversal.
+
+        ``interventional=True`` also keeps the rows themselves (on the device) for
+        ``predict_contribs(..., perturbation="interventional")``, whose first call per
+        ``n_rounds`` reduces them to the per-path mask histogram (csrc/gbdt_iv.hip) --
+        with several ranks that first call is collective.  The torch path loops over
+        the background rows, so with several ranks it gathers every rank's rows here."""
         if X.dim() != 2:
             raise ValueError(f"set_background: X must be [N, F], got {tuple(X.shape)}")
         if self.cuts is not None and X.shape[1] != self.cuts.shape[0]:
@@ -997,6 +1035,13 @@ class HistGBDT:
         _allreduce_(counts)
         self._cover_cache = (self._forest_cache[0], counts, X.shape[1])
         self._paths_cache = self._pairs_cache = None
+        self._iv_bg = self._iv_cache = None
+        if interventional:
+            if _world() > 1 and not (self.use_hip and X.is_cuda):
+                parts = [None] * _world()
+                dist.all_gather_object(parts, X.cpu())
+                X = torch.cat(parts).to(self.device)
+            self._iv_bg = (self._forest_cache[0], X, int(rows))
         return counts
 
     @staticmethod
@@ -1040,6 +1085,7 @@ class HistGBDT:
         p_v, p_m, p_cls = [], [], []                                  # per path
         e_path, e_j, e_f, e_lo, e_hi, e_hl, e_z = [], [], [], [], [], [], []  # per element
         bias = [0.0] * K
+        bias0 = [0.0] * K  # the leaves of single-leaf trees (m = 0): what the interventional bias adds as it is
         for k in range(K):
             for t in range(k, n_rounds * K, K):
                 o, e = offs[t], offs[t + 1]
@@ -1059,6 +1105,8 @@ class HistGBDT:
                         bias[k] += val[i] * z_all
                         if elems:
                             p_v.append(val[i]); p_m.append(len(elems)); p_cls.append(k)
+                        else:
+                            bias0[k] += val[i]
                         continue
                     th, cp = thr[i], cover[o + i]
                     at = next((j for j, el in enumerate(elems) if el[0] == f), -1)
@@ -1119,7 +1167,7 @@ class HistGBDT:
         table = {"slots": torch.from_numpy(slots).to(dev),
                  "chunk_off": torch.tensor(chunk_off, dtype=torch.int32, device=dev),
                  "class_chunk": torch.tensor(class_chunk, dtype=torch.int32, device=dev),
-                 "bias64": [b + base for b in bias], "pad": pad}
+                 "bias64": [b + base for b in bias], "bias0": [b + base for b in bias0], "pad": pad}
         table["bias"] = torch.tensor(table["bias64"], dtype=torch.float32, device=dev)
         self._paths_cache = (key, table)
         return table
@@ -1165,14 +1213,22 @@ class HistGBDT:
         phi[:, :, F] = torch.tensor(table["bias64"], dtype=torch.float64, device=dev)
         return phi.float()
 
-    def predict_contribs(self, X: torch.Tensor, n_rounds: Optional[int] = None) -> torch.Tensor:
+    def predict_contribs(self, X: torch.Tensor, n_rounds: Optional[int] = None,
+                         perturbation: str = "path_dependent") -> torch.Tensor:
         """Per-feature contributions to the raw margin, fp32 [N, K, F + 1]: exact
         path-dependent TreeSHAP with the covers of ``set_background`` (row counts), the
         Shapley values of ``S -> sum over the class's trees of E_t(x, S)``.  Column ``F``
         is the bias (the expected margin over the background plus the base margin); the
         last axis sums to ``predict(X, output_margin=True)`` up to rounding.
         ``n_rounds`` as in ``predict``.  On the GPU this is the contribution kernel of
-        csrc/gbdt_shap.hip, on CPU the same formula on torch ops in fp64."""
+        csrc/gbdt_shap.hip, on CPU the same formula on torch ops in fp64.
+
+        ``perturbation="interventional"``: the interventional (marginal) TreeSHAP of the
+        module docstring over the rows of ``set_background(X, interventional=True)``; the
+        bias is then the mean margin over those rows.  On the GPU the kernels of
+        csrc/gbdt_iv.hip over the mask histogram, on CPU ``_contribs_iv_torch``."""
+        if perturbation not in ("path_dependent", "interventional"):
+            raise ValueError(f"predict_contribs: perturbation {perturbation!r} (path_dependent or interventional)")
         if X.dim() != 2:
             raise ValueError(f"predict_contribs: X must be [N, F], got {tuple(X.shape)}")
         if self.cuts is not None and X.shape[1] != self.cuts.shape[0]:
@@ -1188,12 +1244,187 @@ class HistGBDT:
             raise ValueError(f"predict_contribs: X has {X.shape[1]} features, the background set had "
                              f"{self._cover_cache[2]}")
         X = X.to(self.device).float().contiguous()
+        if perturbation == "interventional":
+            bg = self._iv_bg
+            if bg is None or bg[0] != self._forest_cache[0]:
+                raise ValueError("predict_contribs: perturbation='interventional' needs the background rows of these "
+                                 "trees (call set_background(X, interventional=True) first)")
+            if self.use_hip and X.is_cuda:
+                iv = self._iv_table(n_rounds)
+                out = torch.empty(X.shape[0], self._num_class(), X.shape[1] + 1, dtype=torch.float32,
+                                  device=self.device)
+                _ext.load().gbdt_contribs_iv(X, iv["slots"], iv["chunk_off"], iv["class_chunk"], iv["bias"],
+                                             out.shape[1], out)
+                return out
+            return self._contribs_iv_torch(X, table, bg[1], bg[2])
         if self.use_hip and X.is_cuda:
             out = torch.empty(X.shape[0], self._num_class(), X.shape[1] + 1, dtype=torch.float32, device=self.device)
             _ext.load().gbdt_contribs(X, table["slots"], table["chunk_off"], table["class_chunk"], table["bias"],
                                       out.shape[1], out)
             return out
         return self._contribs_torch(X, table)
+
+    # ------------------------------------------------------------ interventional contributions
+    @staticmethod
+    def _iv_weights():
+        """The Shapley weights of a conjunction game, fp64 [11, 11] each (module docstring):
+        ``Wp[a][b] = (a-1)! b! / (a+b)!`` (a >= 1), ``Wn[a][b] = a! (b-1)! / (a+b)!`` (b >= 1),
+        0 elsewhere and where ``a + b > 10``."""
+        import numpy as np
+        fact = [float(math.factorial(i)) for i in range(11)]
+        wp, wn = np.zeros((11, 11)), np.zeros((11, 11))
+        for a in range(11):
+            for b in range(11 - a):
+                if a:
+                    wp[a, b] = fact[a - 1] * fact[b] / fact[a + b]
+                if b:
+                    wn[a, b] = fact[a] * fact[b - 1] / fact[a + b]
+        return wp, wn
+
+    def _contribs_iv_torch(self, X: torch.Tensor, table: dict, Z: torch.Tensor, B: int) -> torch.Tensor:
+        """``predict_contribs(perturbation="interventional")`` on torch ops, fp64 inside and
+        rounded once: the module docstring's definition evaluated for every (row, background
+        row, path), a block at a time -- the background rows ``Z`` themselves, not their
+        mask histogram.  ``B``: the background rows of all ranks.  The CPU path."""
+        N, F = X.shape
+        K, dev = self._num_class(), X.device
+        pad = {k: torch.from_numpy(v).to(dev) for k, v in table["pad"].items()}
+        P, M = pad["feat"].shape
+        wp, wn = (torch.from_numpy(w).to(dev) for w in self._iv_weights())
+        phi = torch.zeros(N, K * (F + 1), dtype=torch.float64, device=dev)
+        bias = torch.tensor(table["bias0"], dtype=torch.float64, device=dev)
+
+        def inside(R, s):  # [rows, paths, M]: the interval tests, False at the padding
+            xv = R[:, pad["feat"][s].reshape(-1)].view(R.shape[0], -1, M)
+            return ~(xv <= pad["lo"][s]) & (~pad["hl"][s] | (xv <= pad["hi"][s])) & pad["valid"][s]
+        if P:
+            Zd = Z.double()
+            nr, nz = max(min(N, 256), 1), min(Zd.shape[0], 64)
+            pc = max(1, (1 << 22) // (nr * nz * M))
+            for p0 in range(0, P, pc):
+                s = slice(p0, p0 + pc)
+                valid, v = pad["valid"][s], pad["v"][s]
+                idx = (pad["cls"][s][:, None] * (F + 1) + pad["feat"][s]).reshape(-1)
+                full = torch.zeros(v.shape[0], dtype=torch.float64, device=dev)  # background rows that reach the leaf
+                for z0 in range(0, Zd.shape[0], nz):
+                    oz = inside(Zd[z0:z0 + nz], s)
+                    full += (oz | ~valid).all(-1).sum(0)
+                    for r0 in range(0, N, nr):
+                        ox = inside(X[r0:r0 + nr].double(), s)[:, None]  # [n, 1, p, M] against [z, p, M]
+                        reach = (ox | oz | ~valid).all(-1)
+                        D, E = ox & ~oz, oz & ~ox
+                        a, b = D.sum(-1), E.sum(-1)
+                        term = (D * wp[a, b][..., None] - E * wn[a, b][..., None]) * reach[..., None]
+                        term = term.sum(1) * v[:, None]
+                        phi[r0:r0 + ox.shape[0]].index_add_(1, idx, term.reshape(ox.shape[0], -1))
+                bias.index_add_(0, pad["cls"][s], v * full / B)
+            phi /= B
+        phi = phi.view(N, K, F + 1)
+        phi[:, :, F] = bias
+        return phi.float()
+
+    def _iv_table(self, n_rounds: int) -> dict:
+        """The explain table of csrc/gbdt_iv.hip (its header has both layouts) for the first
+        ``n_rounds`` rounds: the background rows are reduced by the mask-histogram kernel to
+        ``hist[path][mask]`` (int64, all-reduced over the ranks), and the masks with a count
+        above 0 are compacted behind each path's elements as records ``{mask, count / B}``.
+        A path with more records than a chunk holds becomes several table paths.  ``bias``:
+        the base margin plus the mean margin over the background, summed in fp64.  Cached
+        beside the path table, under its key."""
+        import numpy as np
+        table = self._path_table(n_rounds)
+        key = self._paths_cache[0]
+        if self._iv_cache is not None and self._iv_cache[0] == key:
+            return self._iv_cache[1]
+        ext, dev, K = _ext.load(), self.device, self._num_class()
+        pad, (_, Z, B) = table["pad"], self._iv_bg
+        m = pad["valid"].sum(1).astype(np.int64)  # a path's elements are its first m
+        P = len(m)
+        hoff = np.concatenate([[0], np.cumsum(np.left_shift(1, m))]).astype(np.int64)  # 2^m counters per path
+        if hoff[-1] >= 2 ** 31:
+            raise ValueError("predict_contribs: mask histogram of 2^31 or more counters")
+
+        def put(slots, head, paths):  # headers { v, m, ., . } and elements of the table paths at ``head``
+            mm = m[paths]
+            g = np.repeat(np.arange(len(paths)), mm)
+            j = np.arange(len(g)) - np.repeat(np.cumsum(mm) - mm, mm)
+            at, sp, fl = head[g] + 1 + j, paths[g], slots.view(np.float32)
+            fl[head, 0] = pad["v"][paths]
+            slots[head, 1] = mm
+            slots[at, 0] = pad["feat"][sp, j] | (pad["hl"][sp, j].astype(np.int64) << 30)
+            fl[at, 1], fl[at, 2] = pad["lo"][sp, j], pad["hi"][sp, j]
+        t0 = self._sync_time()
+        # kernel A's table: chunks of whole paths within both the slot and the counter budget
+        mstart = np.concatenate([[0], np.cumsum(1 + m)]).astype(np.int64)
+        lim_s, lim_c = ext.gbdt_path_masks_chunk_slots(), ext.gbdt_path_masks_chunk_counters()
+        chunk_off, cnt_off = [0], [0]
+        for p in range(P):
+            if mstart[p + 1] - chunk_off[-1] > lim_s or hoff[p + 1] - cnt_off[-1] > lim_c:
+                chunk_off.append(int(mstart[p]))
+                cnt_off.append(int(hoff[p]))
+        if P:
+            chunk_off.append(int(mstart[-1]))
+            cnt_off.append(int(hoff[-1]))
+        mslots = np.zeros((int(mstart[-1]), 4), dtype=np.int32)
+        put(mslots, mstart[:-1], np.arange(P))
+        mslots[mstart[:-1], 2] = hoff[:-1]
+        hist = torch.zeros(int(hoff[-1]), dtype=torch.int64, device=dev)
+        masks = (torch.from_numpy(mslots).to(dev), torch.tensor(chunk_off, dtype=torch.int32, device=dev),
+                 torch.tensor(cnt_off, dtype=torch.int32, device=dev))
+        ext.gbdt_path_masks(Z, *masks, hist)
+        _allreduce_(hist)
+        t1 = self._sync_time()
+        h = hist.cpu().numpy()
+        if P and not (np.add.reduceat(h, hoff[:-1]) == B).all():
+            raise RuntimeError("predict_contribs: a path's mask counters do not sum to the background rows "
+                               "(csrc/gbdt_iv.hip path_masks_kernel)")
+        # records: the masks with a count above 0, in (path, mask) order; w rounds once, from fp64
+        nz = np.flatnonzero(h)
+        rp = np.searchsorted(hoff, nz, side="right") - 1
+        r = np.bincount(rp, minlength=P)
+        limit = ext.gbdt_contribs_iv_chunk_slots()
+        cap = 2 * (limit - 1 - m)  # records one table path can hold
+        pieces = np.maximum((r + cap - 1) // cap, 1)
+        first = np.cumsum(pieces) - pieces
+        pp = np.repeat(np.arange(P), pieces)  # the path of each table path
+        pr = np.minimum(cap[pp], r[pp] - (np.arange(len(pp)) - first[pp]) * cap[pp])
+        start = np.concatenate([[0], np.cumsum(1 + m[pp] + (pr + 1) // 2)]).astype(np.int64)
+        if start[-1] >= 2 ** 29:
+            raise ValueError("predict_contribs: interventional explain table of 2^29 or more slots")
+        cls = pad["cls"][pp]
+        chunk_off, class_chunk, cur = [0], [0] * (K + 1), 0
+        for p in range(len(pp)):  # chunks of whole table paths, none across a class boundary
+            if cls[p] != cur or start[p + 1] - chunk_off[-1] > limit:
+                if start[p] > chunk_off[-1]:
+                    chunk_off.append(int(start[p]))
+                for kk in range(cur + 1, cls[p] + 1):
+                    class_chunk[kk] = len(chunk_off) - 1
+                cur = cls[p]
+        if start[-1] > chunk_off[-1]:
+            chunk_off.append(int(start[-1]))
+        for kk in range(cur + 1, K + 1):
+            class_chunk[kk] = len(chunk_off) - 1
+        slots = np.zeros((int(start[-1]), 4), dtype=np.int32)
+        put(slots, start[:-1], pp)
+        slots[start[:-1], 2] = pr
+        slots[start[:-1], 3] = np.left_shift(1, m[pp]) - 1
+        ri = np.arange(len(rp)) - (np.cumsum(r) - r)[rp]  # the record's index in its path
+        j = ri % cap[rp]
+        at = start[first[rp] + ri // cap[rp]] + 1 + m[rp] + j // 2
+        slots[at, (j % 2) * 2] = nz - hoff[rp]
+        slots.view(np.float32)[at, (j % 2) * 2 + 1] = h[nz] / B
+        # bias: base + paths with m = 0 + v * count(mask == full) / B, in fp64
+        bias = np.asarray(table["bias0"], dtype=np.float64)
+        if P:
+            bias = bias + np.bincount(pad["cls"], weights=pad["v"] * h[hoff[1:] - 1] / B, minlength=K)
+        t2 = self._sync_time()
+        iv = {"slots": torch.from_numpy(slots).to(dev),
+              "chunk_off": torch.tensor(chunk_off, dtype=torch.int32, device=dev),
+              "class_chunk": torch.tensor(class_chunk, dtype=torch.int32, device=dev),
+              "bias": torch.from_numpy(bias.astype(np.float32)).to(dev), "hist": hist, "masks": masks,
+              "paths": P, "table_paths": int(len(pp)), "records": int(len(nz)), "hist_seconds": t1 - t0, "compact_seconds": t2 - t1}
+        self._iv_cache = (key, iv)
+        return iv
 
     # ------------------------------------------------------------ interaction values
     def _pair_table(self, n_rounds: int, F: int) -> dict:

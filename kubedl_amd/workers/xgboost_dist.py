@@ -38,7 +38,8 @@ also writes the per-feature contributions [rows, K, F + 1] of
 ``HistGBDT.predict_contribs`` to ``<model file>.contribs.rank<R>.npy`` (the
 background set is every rank's shard, the covers all-reduced) and adds
 ``contribs_seconds`` and the largest ``|sum of contributions - margin|`` to the
-JSON line.  With ``--pred_interactions`` it writes the SHAP interaction values
+JSON line; ``--feature_perturbation interventional`` makes them the interventional
+TreeSHAP values over the same background (same file).  With ``--pred_interactions`` it writes the SHAP interaction values
 [rows, K, F + 1, F + 1] of ``HistGBDT.predict_interactions`` to
 ``<model file>.interactions.rank<R>.npy``, computed ``--interactions_block_rows`` rows
 at a time (default: blocks of at most 256 MiB) straight into the memory-mapped file,
@@ -156,18 +157,20 @@ def run_predict(args, info) -> int:
     extra = {}
     if args.pred_contribs:
         # the background is every rank's shard: set_background all-reduces the covers
-        model.set_background(X)
-        model.predict_contribs(X)  # code loading + path table
+        iv = args.feature_perturbation == "interventional"
+        kw = {"perturbation": "interventional"} if iv else {}
+        model.set_background(X, **({"interventional": True} if iv else {}))
+        model.predict_contribs(X, **kw)  # code loading + path table (interventional: + the mask histogram)
         sync()
         t0 = time.perf_counter()
-        phi = model.predict_contribs(X)
+        phi = model.predict_contribs(X, **kw)
         sync()
         cdt = kdist.all_reduce_max(time.perf_counter() - t0, info)
         gap = float((phi.double().sum(-1) - margin.double()).abs().max()) if X.shape[0] else 0.0
         contribs_path = f"{path}.contribs.rank{info.rank}.npy"
         np.save(contribs_path, phi.cpu().numpy())
         extra = {"contribs_seconds": cdt, "contribs_max_abs_sum_minus_margin": kdist.all_reduce_max(gap, info),
-                 "contribs": contribs_path}
+                 "contribs": contribs_path, "feature_perturbation": args.feature_perturbation}
     if args.pred_interactions:
         if not args.pred_contribs:
             model.set_background(X)
@@ -219,6 +222,7 @@ def main(argv=None) -> int:
     ap.add_argument("--eval_fraction", type=float, default=0.0)
     ap.add_argument("--early_stopping_rounds", type=int, default=0)
     ap.add_argument("--pred_contribs", action="store_true")
+    ap.add_argument("--feature_perturbation", default="path_dependent", choices=["path_dependent", "interventional"])
     ap.add_argument("--pred_interactions", action="store_true")
     ap.add_argument("--interactions_block_rows", type=int, default=0)
     args, _unknown = ap.parse_known_args(argv)
