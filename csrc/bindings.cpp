@@ -457,7 +457,7 @@ void p2p_allreduce(const std::vector<int64_t>& bufs, const std::vector<int64_t>&
 }
 
 // ------------------------------------------------------------------ GBDT
-std::vector<at::Tensor> gbdt_grad_hess(const at::Tensor& pred, const at::Tensor& y, int64_t obj) {
+std::vector<at::Tensor> gbdt_grad_hess(const at::Tensor& pred, const at::Tensor& y, int64_t obj, double alpha) {
   TORCH_CHECK(pred.is_cuda() && pred.scalar_type() == at::kFloat && pred.dim() == 2 && pred.is_contiguous(),
               "gbdt_grad_hess: pred fp32 [n, K] contiguous");
   TORCH_CHECK(y.scalar_type() == at::kFloat && y.is_contiguous() && y.numel() == pred.size(0),
@@ -465,8 +465,8 @@ std::vector<at::Tensor> gbdt_grad_hess(const at::Tensor& pred, const at::Tensor&
   const c10::hip::HIPGuardMasqueradingAsCUDA guard(pred.device());
   auto g = at::empty_like(pred), h = at::empty_like(pred);
   check_hip(kdl::gbdt_grad_hess(pred.data_ptr<float>(), y.data_ptr<float>(), pred.size(0),
-                                static_cast<int>(pred.size(1)), static_cast<int>(obj), g.data_ptr<float>(),
-                                h.data_ptr<float>(), cur_stream()),
+                                static_cast<int>(pred.size(1)), static_cast<int>(obj), static_cast<float>(alpha),
+                                g.data_ptr<float>(), h.data_ptr<float>(), cur_stream()),
             "gbdt_grad_hess");
   return {g, h};
 }
@@ -2420,7 +2420,9 @@ PYBIND11_MODULE(_C, m) {
   m.def("pack_grads", &pack_grads, "multi-tensor gather of gradient tensors into a flat buffer");
   m.def("pack_grads_ptrs", &pack_grads_ptrs, "pack_grads with the source pointers as kernel arguments");
   m.attr("pack_arg_ptrs") = kdl::kPackArgPtrs;
-  m.def("gbdt_grad_hess", &gbdt_grad_hess, "boosting round gradient + hessian in one launch (0 reg, 1 logistic, 2 softmax)");
+  m.def("gbdt_grad_hess", &gbdt_grad_hess,
+        "boosting round gradient + hessian in one launch (0 reg, 1 logistic, 2 softmax, 3 quantile at alpha)",
+        pybind11::arg("pred"), pybind11::arg("y"), pybind11::arg("obj"), pybind11::arg("alpha") = 0.5);
   m.def("gbdt_hist", &gbdt_hist, "GBDT per-node gradient/hessian histograms (LDS atomics)");
   m.def("gbdt_hist_quant", &gbdt_hist_quant, "the device grower's quantised (fixed-point) histograms (test hook)");
   m.def("set_gbdt_pack64", &kdl::set_gbdt_pack64, "row-per-lane hist: 1 packed 64-bit LDS add, 0 two 32-bit adds, -1 KDL_TUNE");

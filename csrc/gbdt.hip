@@ -985,12 +985,14 @@ __global__ __launch_bounds__(256) void quantise_kernel(const float* __restrict__
 //   obj 0 reg:squarederror   g = p - y,            h = 1
 //   obj 1 binary:logistic    s = 1 / (1 + e^-p),   g = s - y,     h = max(s (1 - s), 1e-16)
 //   obj 2 multi:softprob     s = softmax_k(p),     g = s - [y == k], h = max(2 s (1 - s), 1e-16)
+//   obj 3 reg:quantileerror  g = p > y ? 1 - alpha : -alpha,        h = 1   (pinball loss; the leaves
+//                            are renewed by csrc/gbdt_quantile.hip)
 // pred / g / h are [n, K] row-major (K = 1 except multi); one thread per row.
 // The same fp32 expressions as the torch composition (models/gbdt.py) -- one
 // launch instead of ~5 elementwise kernels per round.
 __global__ __launch_bounds__(256) void grad_hess_kernel(const float* __restrict__ pred, const float* __restrict__ y,
-                                                        int64_t n, int K, int obj, float* __restrict__ g,
-                                                        float* __restrict__ h) {
+                                                        int64_t n, int K, int obj, float alpha,
+                                                        float* __restrict__ g, float* __restrict__ h) {
   const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
   if (i >= n) return;
   const float yi = y[i];
@@ -1003,6 +1005,9 @@ __global__ __launch_bounds__(256) void grad_hess_kernel(const float* __restrict_
     const float s = 1.f / (1.f + expf(-pred[i]));
     g[i] = s - yi;
     h[i] = fmaxf(s * (1.f - s), 1e-16f);
+  } else if (obj == 3) {
+    g[i] = pred[i] > yi ? 1.f - alpha : -alpha;
+    h[i] = 1.f;
   } else {
     float mx = -INFINITY;
     for (int k = 0; k < K; ++k) mx = fmaxf(mx, pred[i * K + k]);
@@ -1079,12 +1084,12 @@ __global__ __launch_bounds__(256) void heap_pack_kernel(const int32_t* __restric
 
 }  // namespace
 
-hipError_t gbdt_grad_hess(const float* pred, const float* y, int64_t n, int K, int obj, float* g, float* h,
-                          hipStream_t s) {
+hipError_t gbdt_grad_hess(const float* pred, const float* y, int64_t n, int K, int obj, float alpha, float* g,
+                          float* h, hipStream_t s) {
   if (n <= 0) return hipSuccess;
-  if (obj < 0 || obj > 2 || K < 1 || (obj == 1 && K != 1)) return hipErrorInvalidValue;
+  if (obj < 0 || obj > 3 || K < 1 || ((obj == 1 || obj == 3) && K != 1)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(grad_hess_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, s, pred, y, n, K,
-                     obj, g, h);
+                     obj, alpha, g, h);
   return hipGetLastError();
 }
 

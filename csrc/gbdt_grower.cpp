@@ -247,6 +247,72 @@ class GbdtGrower {
     }
   }
 
+  // ---- adaptive leaves (reg:absoluteerror / reg:quantileerror, csrc/gbdt_quantile.hip): after the
+  // last level every leaf's value becomes learning_rate * the alpha-quantile of the residuals
+  // y[r] - pred[r, k] of its rows, over the Newton value that gbdt_decide wrote.
+  // One pass's digit counts of this rank's rows, int64 [2^max_depth, digits] (pass 0 also plans the
+  // leaves' segments and forms the keys): all-reduce it before ``leaf_step`` when ranks > 1.
+  at::Tensor leaf_count(int64_t pass, const at::Tensor& y, const at::Tensor& pred, int64_t k) {
+    TORCH_CHECK(pass >= 0 && pass < kdl::gbdt_quantile_passes(), "GbdtGrower.leaf_count: 0 <= pass < ",
+                kdl::gbdt_quantile_passes());
+    TORCH_CHECK(y.is_cuda() && y.scalar_type() == at::kFloat && y.is_contiguous() && y.numel() == N_ &&
+                    y.device() == bins_.device(),
+                "GbdtGrower.leaf_count: y must be contiguous fp32 [N] on the bins' device");
+    TORCH_CHECK(pred.is_cuda() && pred.scalar_type() == at::kFloat && pred.is_contiguous() && pred.dim() == 2 &&
+                    pred.size(0) == N_ && k >= 0 && k < pred.size(1) && pred.device() == bins_.device(),
+                "GbdtGrower.leaf_count: pred [N, K] fp32 contiguous, 0 <= k < K");
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(bins_.device());
+    const int S = 1 << D_;
+    if (!q_hist_.defined()) {
+      auto io = bins_.options().dtype(at::kInt);
+      q_lo_ = at::zeros({S}, io);
+      q_hi_ = at::zeros({S}, io);
+      q_node_ = at::zeros({S}, io);
+      q_chunk_off_ = at::zeros({S + 1}, io);
+      q_prefix_ = at::zeros({S}, io);
+      q_keys_ = at::empty({std::max(N_, 1)}, io);
+      q_target_ = at::zeros({S}, io.dtype(at::kLong));
+      q_hist_ = at::zeros({S, kdl::gbdt_quantile_digits()}, io.dtype(at::kLong));  // every step zeroes it again
+    }
+    if (pass == 0) {
+      kdl::GbdtLevelSegs lv{};
+      for (int d = 0; d <= D_; ++d) {
+        lv.lo[d] = ip(lo_[d]);
+        lv.hi[d] = ip(hi_[d]);
+        lv.exists[d] = ip(exists_[d]);
+      }
+      ck(kdl::gbdt_quantile_leaf_plan(lv, ip(feat_), D_, N_, S, ip(q_lo_), ip(q_hi_), ip(q_node_), ip(q_chunk_off_),
+                                      stream()),
+         "gbdt_quantile_leaf_plan");
+    }
+    ck(kdl::gbdt_quantile_count(static_cast<int>(pass), fp(y), fp(pred), static_cast<int>(pred.size(1)),
+                                static_cast<int>(k), ip(rows_), reinterpret_cast<uint32_t*>(ip(q_keys_)), N_, ip(q_lo_),
+                                ip(q_hi_), ip(q_chunk_off_), S, reinterpret_cast<uint32_t*>(ip(q_prefix_)),
+                                q_hist_.data_ptr<int64_t>(), stream()),
+       "gbdt_quantile_count");
+    return q_hist_;
+  }
+  // The pass's digit from the (global) counts; the last pass writes the leaf values.
+  void leaf_step(int64_t pass, double alpha) {
+    TORCH_CHECK(q_hist_.defined(), "GbdtGrower.leaf_step: leaf_count first");
+    TORCH_CHECK(pass >= 0 && pass < kdl::gbdt_quantile_passes(), "GbdtGrower.leaf_step: 0 <= pass < ",
+                kdl::gbdt_quantile_passes());
+    TORCH_CHECK(alpha >= 0.0 && alpha <= 1.0, "GbdtGrower.leaf_step: alpha must lie in [0, 1]");
+    const c10::hip::HIPGuardMasqueradingAsCUDA guard(bins_.device());
+    ck(kdl::gbdt_quantile_step(static_cast<int>(pass), alpha, q_hist_.data_ptr<int64_t>(), 1 << D_,
+                               reinterpret_cast<uint32_t*>(ip(q_prefix_)), q_target_.data_ptr<int64_t>(), ip(q_node_),
+                               lr_, fp(val_), stream()),
+       "gbdt_quantile_step");
+  }
+  // All passes back to back (one rank).
+  void renew_leaves(const at::Tensor& y, const at::Tensor& pred, int64_t k, double alpha) {
+    TORCH_CHECK(alpha >= 0.0 && alpha <= 1.0, "GbdtGrower.renew_leaves: alpha must lie in [0, 1]");
+    for (int p = 0; p < kdl::gbdt_quantile_passes(); ++p) {
+      leaf_count(p, y, pred, k);
+      leaf_step(p, alpha);
+    }
+  }
+
   // the row-indexed leaf of every row, as of the last add_leaf
   at::Tensor node_of_row() const { return node_of_row_; }
   // pred[:, k] += leaf value of each row (pred [N, K] fp32 contiguous)
@@ -310,6 +376,8 @@ class GbdtGrower {
   at::Tensor split_, gain_, sbin_, gl_, hl_, tot_, feat_, tbin_, thr_, val_;
   at::Tensor hist_cur_, hist_next_, built_, cnt_, build_child_, blo_, bhi_, chunk_off_, gh_max_;
   at::Tensor scan_status_, scan_ticket_, scan_fault_, tile_cnt_, tile_off_, node_base_, node_r_;
+  // leaf renewal (allocated by the first leaf_count): leaf segments, chunk prefix, select state
+  at::Tensor q_lo_, q_hi_, q_node_, q_chunk_off_, q_prefix_, q_keys_, q_target_, q_hist_;
   uint32_t scan_epoch_ = 0;
   // KDL_TUNE gbdt_route_scan (default 0): 1 = the fused route + look-back scan (one launch; measured
   // slower: 59.9 us per level against 23.0 + 14.6 for route_flags + the device scan, 941-952 vs
@@ -412,6 +480,42 @@ std::vector<at::Tensor> gbdt_level_test(const at::Tensor& bins, const at::Tensor
   return {rn, pn, lon, hin, cnt, bc, blo, bhi};
 }
 
+// out fp32 [S]: sorted(keys[seg_lo[s] : seg_hi[s]])[max(ceil(alpha * n_s) - 1, 0)] of every segment, 0 for an
+// empty one (csrc/gbdt_quantile.hip; exact, bit-reproducible).  The segments are disjoint ranges of positions
+// (bounds outside [0, n] are clamped); keys are NaN-free: the caller's contract.
+at::Tensor gbdt_segment_quantile(const at::Tensor& keys, const at::Tensor& seg_lo, const at::Tensor& seg_hi,
+                                 double alpha) {
+  TORCH_CHECK(keys.is_cuda() && keys.scalar_type() == at::kFloat && keys.dim() == 1 && keys.is_contiguous(),
+              "gbdt_segment_quantile: keys must be a contiguous fp32 [n] GPU tensor");
+  TORCH_CHECK(keys.numel() < (1LL << 31), "gbdt_segment_quantile: n must fit in int32");
+  for (const at::Tensor* t : {&seg_lo, &seg_hi})
+    TORCH_CHECK(t->is_cuda() && t->device() == keys.device() && t->scalar_type() == at::kInt && t->dim() == 1 &&
+                    t->is_contiguous(),
+                "gbdt_segment_quantile: seg_lo / seg_hi must be contiguous int32 [S] on the keys' device");
+  const int64_t S = seg_lo.numel();
+  TORCH_CHECK(seg_hi.numel() == S && S >= 1 && S <= kdl::gbdt_quantile_max_segments(),
+              "gbdt_segment_quantile: 1 <= S <= ", kdl::gbdt_quantile_max_segments(), ", seg_lo and seg_hi alike");
+  TORCH_CHECK(alpha >= 0.0 && alpha <= 1.0, "gbdt_segment_quantile: alpha must lie in [0, 1]");
+  const c10::hip::HIPGuardMasqueradingAsCUDA guard(keys.device());
+  const int n = static_cast<int>(keys.numel()), s = static_cast<int>(S);
+  auto io = seg_lo.options();
+  auto chunk_off = at::empty({S + 1}, io), prefix = at::empty({S}, io), ukeys = at::empty({std::max(n, 1)}, io);
+  auto target = at::empty({S}, io.dtype(at::kLong));
+  auto hist = at::zeros({S, kdl::gbdt_quantile_digits()}, io.dtype(at::kLong));
+  auto out = at::empty({S}, keys.options());
+  ck(kdl::gbdt_quantile_plan(ip(seg_lo), ip(seg_hi), s, n, ip(chunk_off), stream()), "gbdt_quantile_plan");
+  for (int p = 0; p < kdl::gbdt_quantile_passes(); ++p) {
+    ck(kdl::gbdt_quantile_count(p, fp(keys), nullptr, 1, 0, nullptr, reinterpret_cast<uint32_t*>(ip(ukeys)), n,
+                                ip(seg_lo), ip(seg_hi), ip(chunk_off), s, reinterpret_cast<uint32_t*>(ip(prefix)),
+                                hist.data_ptr<int64_t>(), stream()),
+       "gbdt_quantile_count");
+    ck(kdl::gbdt_quantile_step(p, alpha, hist.data_ptr<int64_t>(), s, reinterpret_cast<uint32_t*>(ip(prefix)),
+                               target.data_ptr<int64_t>(), nullptr, 1.f, fp(out), stream()),
+       "gbdt_quantile_step");
+  }
+  return out;
+}
+
 at::Tensor gbdt_quantise(const at::Tensor& X, const at::Tensor& cuts, int64_t num_bins) {
   TORCH_CHECK(X.is_cuda() && X.dim() == 2, "gbdt_quantise: X [N, F] on the GPU");
   const c10::hip::HIPGuardMasqueradingAsCUDA guard(X.device());
@@ -440,6 +544,9 @@ void register_gbdt(pybind11::module& m) {
       .def("level_b", &GbdtGrower::level_b)
       .def("level_c", &GbdtGrower::level_c)
       .def("grow_local", &GbdtGrower::grow_local)
+      .def("leaf_count", &GbdtGrower::leaf_count, py::arg("pass"), py::arg("y"), py::arg("pred"), py::arg("k"))
+      .def("leaf_step", &GbdtGrower::leaf_step, py::arg("pass"), py::arg("alpha"))
+      .def("renew_leaves", &GbdtGrower::renew_leaves, py::arg("y"), py::arg("pred"), py::arg("k"), py::arg("alpha"))
       .def("node_of_row", &GbdtGrower::node_of_row)
       .def("add_leaf", &GbdtGrower::add_leaf)
       .def("heap_packed", &GbdtGrower::heap_packed)
@@ -455,6 +562,10 @@ void register_gbdt(pybind11::module& m) {
       .def_static("set_route_scan", [](int v) { GbdtGrower::g_route_scan = v; },
                   "1: fused route + look-back scan, 0: route_flags + device scan, -1: KDL_TUNE gbdt_route_scan");
   m.def("gbdt_quantise", &gbdt_quantise, "GBDT feature quantisation (bins = #cuts < x, clamped)");
+  m.def("gbdt_segment_quantile", &gbdt_segment_quantile,
+        "exact alpha-quantile (rank max(ceil(alpha n) - 1, 0)) of every segment of fp32 keys", py::arg("keys"),
+        py::arg("seg_lo"), py::arg("seg_hi"), py::arg("alpha"));
+  m.def("gbdt_quantile_chunk_rows", &kdl::gbdt_quantile_chunk_rows, "positions per block of the select's count kernel");
   m.def("gbdt_level_test", &gbdt_level_test, "one level's partition + child segments: three-launch plan or scan path");
   m.def("gbdt_route_scan_test", &gbdt_route_scan_test, "(flag, inclusive scan) of a level's routing: fused or two-pass",
         py::arg("bins"), py::arg("rows"), py::arg("node_pos"), py::arg("split"), py::arg("t_feat"), py::arg("t_bin"),

@@ -183,9 +183,9 @@ hipError_t p2p_allreduce(const P2PArgs& a, bool bf16, bool oneshot, hipStream_t 
 
 // ---- gbdt.hip (histogram GBDT for the XGBoostJob worker)
 // one boosting round's gradient / hessian (obj 0 reg:squarederror, 1 binary:logistic,
-// 2 multi:softprob; pred / g / h [n, K] fp32, y [n] fp32 labels / class ids)
-hipError_t gbdt_grad_hess(const float* pred, const float* y, int64_t n, int K, int obj, float* g, float* h,
-                          hipStream_t s);
+// 2 multi:softprob, 3 reg:quantileerror at ``alpha``; pred / g / h [n, K] fp32, y [n] fp32 labels / class ids)
+hipError_t gbdt_grad_hess(const float* pred, const float* y, int64_t n, int K, int obj, float alpha, float* g,
+                          float* h, hipStream_t s);
 hipError_t gbdt_hist_build(const uint8_t* bins, const float* grad, const float* hess, int64_t gh_stride,
                            const int32_t* rows, const int32_t* seg, int num_nodes, int max_rows_per_node,
                            int F, int B, float* hist, hipStream_t s);
@@ -338,6 +338,40 @@ hipError_t gbdt_rank_ndcg(const float* score, const int32_t* label, int64_t N, c
 int gbdt_rank_wave_max();    // the largest group of the wave path (64)
 int gbdt_rank_tile_rows();   // rows per block item (256)
 int gbdt_rank_chunk_rows();  // j rows per LDS chunk (1024)
+
+// ---- gbdt_quantile.hip (reg:absoluteerror / reg:quantileerror: the exact segmented quantile select)
+// Segment s owns positions [seg_lo[s], seg_hi[s]) (disjoint, clamped to [0, n]); per pass (0 ..
+// gbdt_quantile_passes() - 1) gbdt_quantile_count adds the digit counts to hist int64 [S, gbdt_quantile_digits()]
+// (zero before pass 0; all-reduce it between the two calls with several ranks) and gbdt_quantile_step
+// advances prefix uint32 [S] / target int64 [S] and zeroes hist; after the last pass out holds
+// sorted(keys of s)[max(ceil(alpha * n_s) - 1, 0)], 0 for an empty segment (definition: the file's header).
+constexpr int kGbdtLevels = 11;  // tree levels of the device grower (max_depth <= 10)
+struct GbdtLevelSegs {           // the grower's per-level node segments and existence flags
+  const int32_t* lo[kGbdtLevels];
+  const int32_t* hi[kGbdtLevels];
+  const int32_t* exists[kGbdtLevels];
+};
+int gbdt_quantile_chunk_rows();    // positions per block (2048)
+int gbdt_quantile_digits();        // 256
+int gbdt_quantile_passes();        // 4
+int gbdt_quantile_max_segments();  // 1024
+// chunk_off int32 [S + 1]: the chunk prefix of the count kernel's work split
+hipError_t gbdt_quantile_plan(const int32_t* seg_lo, const int32_t* seg_hi, int S, int n, int32_t* chunk_off,
+                              hipStream_t s);
+// the current tree's leaves in heap order as segments (seg_lo / seg_hi / seg_node int32 [S], S >= 2^D; unused
+// slots empty with node -1) and their chunk prefix
+hipError_t gbdt_quantile_leaf_plan(const GbdtLevelSegs& lv, const int32_t* t_feat, int D, int n, int S,
+                                   int32_t* seg_lo, int32_t* seg_hi, int32_t* seg_node, int32_t* chunk_off,
+                                   hipStream_t s);
+// pass 0 forms key[p] = y[r] - pred[r * ld + k], r = rows[p] (pred == nullptr: y[r]; rows == nullptr: r = p) and
+// stores its ordered image in ukeys [n]; later passes read ukeys only
+hipError_t gbdt_quantile_count(int pass, const float* y, const float* pred, int ld, int k, const int32_t* rows,
+                               uint32_t* ukeys, int n, const int32_t* seg_lo, const int32_t* seg_hi,
+                               const int32_t* chunk_off, int S, const uint32_t* prefix, int64_t* hist,
+                               hipStream_t s);
+// seg_node == nullptr: out[s] = q; else out[seg_node[s]] = scale * q for seg_node[s] >= 0
+hipError_t gbdt_quantile_step(int pass, double alpha, int64_t* hist, int S, uint32_t* prefix, int64_t* target,
+                              const int32_t* seg_node, float scale, float* out, hipStream_t s);
 
 // ---- ctr.hip (XDLJob CTR model: MFMA GEMM, embeddings, sparse Adagrad)
 // b_kn: B is [K][N] (C = A B), else [N][K] (C = A B^T)

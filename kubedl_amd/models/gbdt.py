@@ -125,6 +125,23 @@ definition, shared by both paths and by the tests:
   pos_i < k of G(y_i) * D[pos_i]`` in fp64; a group whose ``IDCG@k`` is 0 counts as
   1), ``k = GBDTParams.eval_at``, 0 = the whole list; the metric is named ``ndcg`` for
   ``k = 0`` and ``ndcg@k`` otherwise.  Higher is better: early stopping maximises it.
+
+Robust and quantile regression: objectives ``reg:absoluteerror`` (alpha = 0.5) and
+``reg:quantileerror`` (``GBDTParams.quantile_alpha``), the pinball loss.  Its gradient is one
+of two constants (``g = pred > y ? 1 - alpha : -alpha``, ``h = 1``) and carries no leaf
+value, so the tree's structure is grown on (g, h) and every leaf is then renewed
+(XGBoost's adaptive leaves): ``value = fp32(learning_rate) * q`` (one fp32 multiply), ``q``
+the alpha-quantile of the residuals ``y[r] - margin[r]`` (one fp32 subtraction, the margin
+before the tree) of the rows r of all ranks that ended in the leaf.  The alpha-quantile
+of n keys is ``sorted(keys)[t]`` with ``t = max(ceil(alpha * n) - 1, 0)``, the product and
+the ceil in fp64 -- an element of the input, never an interpolation; keys are ordered
+as floats (-0 and +0 tie) and must not be NaN; an empty leaf gets 0.  The base margin is
+the same quantile of y over all ranks, stored in ``base_score`` by ``fit``.  On the GPU
+the select is csrc/gbdt_quantile.hip (a radix select over 8-bit digits of the ordered
+bit pattern: per pass a count kernel, the integer all-reduce of its [leaves, 256] table
+when there are several ranks, and a step kernel); on CPU ``_select_torch`` runs the same
+passes with ``bincount``.  Metrics: ``mae`` and ``quantile`` (the mean pinball loss
+``max(alpha d, (alpha - 1) d)``, ``d = y - pred``); lower is better.
 """
 from __future__ import annotations
 
@@ -141,6 +158,8 @@ import torch.distributed as dist
 from kubedl_amd.ops import _ext
 
 RANK_OBJECTIVES = ("rank:pairwise", "rank:ndcg")
+QUANTILE_OBJECTIVES = ("reg:absoluteerror", "reg:quantileerror")
+QUANTILE_PASSES = 4  # 8-bit digits of the 32-bit key (csrc/gbdt_quantile.hip)
 MAX_RANK_LABEL = 31
 
 
@@ -158,6 +177,7 @@ class GBDTParams:
     base_score: float = 0.5
     early_stopping_rounds: int = 0  # 0 = off (fit's ``early_stopping_rounds`` argument overrides it)
     eval_at: int = 0  # ranking objectives: the k of ndcg@k, 0 = the whole list
+    quantile_alpha: float = 0.5  # reg:quantileerror: the quantile to fit, in (0, 1)
 
     @classmethod
     def parse(cls, spec: str, **kw) -> "GBDTParams":
@@ -308,15 +328,22 @@ class HistGBDT:
                 return g, h
             g, h, _ = self._rank_grad_hess_torch(pred.view(-1), rank)
             return g.view(-1, 1), h.view(-1, 1)
+        quant = obj in QUANTILE_OBJECTIVES
         if self.use_hip and pred.is_cuda:
             # csrc/gbdt.hip grad_hess_kernel: one launch, the torch composition's expressions
-            code = 0 if obj.startswith("reg:") else 1 if obj == "binary:logistic" else 2 if obj.startswith("multi:") else -1
+            code = 3 if quant else 0 if obj.startswith("reg:") else 1 if obj == "binary:logistic" else 2 if obj.startswith("multi:") else -1
             if code >= 0:
                 c = getattr(self, "_yf", None)
                 if c is None or c[0] is not y:  # the labels as fp32, converted once per fit
                     c = self._yf = (y, y if (y.dtype == torch.float32 and y.is_contiguous()) else y.float().contiguous())
+                if quant:
+                    return _ext.load().gbdt_grad_hess(pred.contiguous(), c[1].view(-1), code, self._alpha())
                 g, h = _ext.load().gbdt_grad_hess(pred.contiguous(), c[1].view(-1), code)
                 return g, h
+        if quant:
+            a = self._alpha()
+            up = pred > y.view_as(pred).float()
+            return torch.where(up, 1.0 - a, -a).to(torch.float32), torch.ones_like(pred)
         if obj.startswith("reg:"):
             return pred - y.view_as(pred), torch.ones_like(pred)
         if obj == "binary:logistic":
@@ -337,6 +364,53 @@ class HistGBDT:
         else:
             b = self.p.base_score
         return torch.full((n, K), b, dtype=torch.float32, device=self.device)
+
+    # ------------------------------------------------------------ quantile objectives
+    def _alpha(self) -> float:
+        return 0.5 if self.p.objective == "reg:absoluteerror" else float(self.p.quantile_alpha)
+
+    @staticmethod
+    def _select_torch(keys: torch.Tensor, seg: torch.Tensor, S: int, alpha: float) -> torch.Tensor:
+        """fp32 [S]: the alpha-quantile (module docstring) of the fp32 ``keys`` of every segment,
+        ``seg`` [n] holding each key's segment id, counted over all ranks; 0 for an empty
+        segment.  The digit passes of csrc/gbdt_quantile.hip on torch ops: the CPU path, which
+        serves gloo ranks too."""
+        b = keys.contiguous().view(torch.int32).long() & 0xFFFFFFFF
+        u = torch.where(b >= 1 << 31, b ^ 0xFFFFFFFF, b | (1 << 31))  # unsigned order = float order
+        seg = seg.long()
+        prefix = torch.zeros(S, dtype=torch.int64, device=keys.device)
+        n_s = t = None
+        for p in range(QUANTILE_PASSES):
+            shift = 24 - 8 * p
+            m = (u >> (shift + 8)) == prefix[seg]  # pass 0: every key (0 == 0)
+            hist = _allreduce_(torch.bincount(seg[m] * 256 + ((u[m] >> shift) & 255), minlength=S * 256)).view(S, 256)
+            if p == 0:
+                n_s = hist.sum(1)
+                t = (torch.ceil(alpha * n_s.double()).long() - 1).clamp_(min=0)
+            cum = hist.cumsum(1)
+            d = (cum <= t[:, None]).sum(1).clamp_(max=255)[:, None]  # the first digit whose count passes t
+            t = t - (cum.gather(1, d) - hist.gather(1, d))[:, 0]
+            prefix = prefix * 256 + d[:, 0]
+        bits = torch.where(prefix >= 1 << 31, prefix ^ (1 << 31), prefix ^ 0xFFFFFFFF)
+        q = (bits - ((bits >= 1 << 31).long() << 32)).int().view(torch.float32)
+        return torch.where(n_s > 0, q, torch.zeros_like(q))
+
+    def _quantile_of(self, yf: torch.Tensor, alpha: float) -> float:
+        """The alpha-quantile of every rank's labels (the base margin)."""
+        n = yf.shape[0]
+        if self.use_hip and yf.is_cuda and _world() == 1:
+            b = torch.tensor([0, n], dtype=torch.int32, device=yf.device)
+            return float(_ext.load().gbdt_segment_quantile(yf, b[:1], b[1:], alpha))
+        return float(self._select_torch(yf, torch.zeros(n, dtype=torch.int64, device=yf.device), 1, alpha))
+
+    def _renew_leaves_torch(self, tree: "Tree", leaf: torch.Tensor, yf: torch.Tensor, margin: torch.Tensor) -> None:
+        """Adaptive leaves on torch ops: every leaf of ``tree`` becomes fp32(lr) * the quantile of
+        the residuals of the rows that ``leaf`` (the tree node of each row) puts in it."""
+        q = self._select_torch(yf - margin, leaf, len(tree.value), self._alpha())
+        vals = (q * torch.tensor(self.p.learning_rate, dtype=torch.float32, device=q.device)).tolist()
+        for nid, f in enumerate(tree.feature):
+            if f < 0:
+                tree.value[nid] = vals[nid]
 
     # ------------------------------------------------------------ learning to rank
     def _ndcg_name(self) -> str:
@@ -630,9 +704,10 @@ class HistGBDT:
         return _ext.load().GbdtGrower(bins, self.cuts, p.max_bin, p.max_depth, p.reg_lambda, p.gamma,
                                       p.learning_rate, p.min_child_weight)
 
-    def _grow_device(self, gr, g, h):
+    def _grow_device(self, gr, g, h, renew=None):
         """One tree on the GPU; returns its [4, heap] arrays (feature, split bin,
-        threshold, value)."""
+        threshold, value).  ``renew = (y, margin, k, alpha)``: the quantile objectives'
+        leaf renewal after the last level, its count tables all-reduced pass by pass."""
         D = self.p.max_depth
         if _world() == 1:
             gr.grow_local(g, h)
@@ -644,6 +719,14 @@ class HistGBDT:
                     _allreduce_(cnt)                    # global child counts -> same smaller child on all ranks
                     _allreduce_(gr.level_b(d, True))    # the built children's histograms
                     gr.level_c(d)
+        if renew is not None:
+            yf, margin, k, alpha = renew
+            if _world() == 1:
+                gr.renew_leaves(yf, margin, k, alpha)
+            else:
+                for ps in range(QUANTILE_PASSES):
+                    _allreduce_(gr.leaf_count(ps, yf, margin, k))  # global counts -> the same leaves on all ranks
+                    gr.leaf_step(ps, alpha)
         return gr.heap_packed()  # [4, heap] in one launch (the leaf values go in by add_leaf)
 
     @staticmethod
@@ -672,7 +755,7 @@ class HistGBDT:
 
         ``eval_set=(Xv, yv)``: a held-out set (this rank's shard of it) whose margin is
         advanced by each round's trees; ``evals_result[i]`` is the objective's metric
-        (``eval_metric``: rmse / logloss / mlogloss) after round ``i``, from loss sums
+        (``eval_metric``: rmse / logloss / mlogloss / mae / quantile) after round ``i``, from loss sums
         all-reduced over the ranks.  Without ``early_stopping_rounds`` the sums stay
         on the device until the end of ``fit`` (one copy); with it one value is read
         per round, training stops once the metric has not improved for that many
@@ -689,6 +772,14 @@ class HistGBDT:
             raise ValueError(f"group is for the ranking objectives, not {self.p.objective}")
         if ranking and X.shape[0] != y.shape[0]:
             raise ValueError(f"fit: {X.shape[0]} rows of X for {y.shape[0]} labels")
+        quant = self.p.objective in QUANTILE_OBJECTIVES
+        if quant:
+            if not 0.0 < self._alpha() < 1.0:
+                raise ValueError(f"{self.p.objective}: quantile_alpha must lie in (0, 1), got {self.p.quantile_alpha}")
+            if y.numel() != X.shape[0]:
+                raise ValueError(f"fit: {X.shape[0]} rows of X for {y.numel()} labels")
+            if y.dtype.is_floating_point and bool(torch.isnan(y).any()):
+                raise ValueError(f"{self.p.objective}: NaN label")
         t0 = self._sync_time()
         host_cuts = {}
         th = None
@@ -720,6 +811,10 @@ class HistGBDT:
         tb = self._sync_time()
         bins = self.quantise(X).contiguous()
         n = X.shape[0]
+        yq = None
+        if quant:  # the base margin: the labels' quantile over all ranks, kept in the parameters
+            yq = y.reshape(-1).float().contiguous()
+            self.p.base_score = self._quantile_of(yq, self._alpha())
         pred = self._base(n)
         K = pred.shape[1]
         tc = self._sync_time()
@@ -738,10 +833,13 @@ class HistGBDT:
                 g = g_all[:, k].contiguous()
                 h = h_all[:, k].contiguous()
                 if grower is not None:
-                    round_trees.append(self._grow_device(grower, g, h))
+                    renew = (yq, pred, k, self._alpha()) if quant else None
+                    round_trees.append(self._grow_device(grower, g, h, renew))
                     grower.add_leaf(pred, k)  # pred[:, k] += the rows' leaf values, one launch
                     continue
                 tree, leaf = self._grow(bins, g, h, n)
+                if quant:
+                    self._renew_leaves_torch(tree, leaf, yq, pred[:, k])
                 vals = torch.tensor(tree.value, dtype=torch.float32, device=self.device)
                 pred[:, k] += vals[leaf.long()]
                 round_trees.append(tree)
@@ -788,6 +886,9 @@ class HistGBDT:
             pr = torch.sigmoid(margin[:, 0])
             yy = y.float()
             row = -(yy * torch.log(pr.clamp_min(1e-15)) + (1 - yy) * torch.log((1 - pr).clamp_min(1e-15)))
+        elif obj in QUANTILE_OBJECTIVES:  # mae: the absolute error; quantile: the pinball loss
+            a, d = self._alpha(), y.reshape(-1).double() - margin[:, 0].double()
+            row = d.abs() if obj == "reg:absoluteerror" else torch.maximum(a * d, (a - 1.0) * d)
         else:
             row = (margin[:, 0] - y.float()) ** 2
         return row.sum(dtype=torch.float64)
@@ -805,7 +906,8 @@ class HistGBDT:
         K = self._num_class()
         esr = self.p.early_stopping_rounds if early_stopping_rounds is None else early_stopping_rounds
         obj = self.p.objective
-        self.eval_metric = "mlogloss" if obj.startswith("multi:") else "logloss" if obj == "binary:logistic" else "rmse"
+        self.eval_metric = "mlogloss" if obj.startswith("multi:") else "logloss" if obj == "binary:logistic" else \
+            "mae" if obj == "reg:absoluteerror" else "quantile" if obj == "reg:quantileerror" else "rmse"
         self.evals_result = []
         self.best_iteration = self.best_score = None
         count = float(Xv.shape[0])
@@ -1635,4 +1737,7 @@ class HistGBDT:
             yy = y.float()
             ll = -(yy * torch.log(pr.clamp_min(1e-15)) + (1 - yy) * torch.log((1 - pr).clamp_min(1e-15))).mean()
             return {"logloss": float(ll), "accuracy": float(((pr > 0.5).float() == yy).float().mean())}
+        if obj in QUANTILE_OBJECTIVES:
+            name = "mae" if obj == "reg:absoluteerror" else "quantile"
+            return {name: float(self._loss_sum(pred.reshape(pred.shape[0], -1), y)) / max(pred.shape[0], 1)}
         return {"rmse": float(torch.sqrt(((pred[:, 0] - y.float()) ** 2).mean()))}

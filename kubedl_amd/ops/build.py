@@ -50,10 +50,12 @@ def _common_flags(abi: int):
 # extra flags per HIP source.  gbdt_shap.hip: plain fp32 ops only (no packed v_pk_*_f32 pairs), so
 # that every product and sum rounds once, as the error bound of tests/test_gbdt_contribs.py counts them
 # gbdt_rank.hip: the same, for the bound of tests/test_gbdt_rank.py; gbdt_interactions.hip: for
-# tests/test_gbdt_interactions.py; gbdt_iv.hip: for tests/test_gbdt_iv.py
+# tests/test_gbdt_interactions.py; gbdt_iv.hip: for tests/test_gbdt_iv.py; gbdt_quantile.hip: the residual
+# is one fp32 subtraction and the leaf one fp32 multiply, as tests/test_gbdt_quantile.py recomputes them
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 FILE_FLAGS = {"gbdt_shap.hip": _NO_PACKED_FP32, "gbdt_rank.hip": _NO_PACKED_FP32,
-              "gbdt_interactions.hip": _NO_PACKED_FP32, "gbdt_iv.hip": _NO_PACKED_FP32}
+              "gbdt_interactions.hip": _NO_PACKED_FP32, "gbdt_iv.hip": _NO_PACKED_FP32,
+              "gbdt_quantile.hip": _NO_PACKED_FP32}
 
 
 def _headers_digest() -> str:

@@ -17,7 +17,12 @@ rows per rank with a nonlinear target, HIGGS-like shape).  With
 ``--group_size`` rows (``load_groups``: fixed seed, whole groups on every rank), the
 label is a 0-4 relevance grade, the default objective ``rank:ndcg``, and Train and
 Predict both report ``ndcg@k`` (``eval_at:k`` in ``--xgboost_parameter``; ``ndcg`` for
-the whole list); ``--eval_fraction`` then holds out whole groups.
+the whole list); ``--eval_fraction`` then holds out whole groups.  With
+``--objective_hint reg`` the target is the noisy nonlinear function itself, for
+``reg:squarederror`` (the default), ``reg:absoluteerror`` and ``reg:quantileerror``
+(``quantile_alpha:a`` in ``--xgboost_parameter``; the reported metric is ``mae`` or the mean
+pinball loss ``quantile``; ``examples/xgboost/quantile_train.yaml`` fits a 0.1 and a 0.9
+quantile model of the same rows).
 
 ``--job_type=Train`` (the default) fits a model, prints one JSON line with the
 training metric and rounds/s, and rank 0 writes the model to ``--model_path``
